@@ -11,7 +11,11 @@ timed region.  N=1 workload: BASELINE.json configs[1], wdl_criteo bs=256 d=512, 
 table in HBM.  N>1: the table is row-range sharded over the ranks (AveragePartitioner ranges) and
 ids / rows / reduced gradients cross ranks with RCCL all-to-all (herald_amd.sharded).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
+Prints ONE JSON line on rank 0.  A plain run measures the headline and nothing else: it sets up, warms up, times --steps
+steps and prints the line.  --full adds every secondary figure (CPU baseline, per-kernel pass, bit-exact engine and lookahead
+sweep, cache / laia / wide / cold-tier lines; N>1: configs[2]'s shape, the same-path world-1 figure, per-kernel times);
+the --no-* options switch single parts of it off.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -102,7 +106,16 @@ def parse_args():
     p.add_argument("--grad-buffers", type=int, default=24,
                    help="distinct gradient / output buffers cycled through (24 x 13.6 MB = 327 MB > the "
                         "256 MiB Infinity Cache, so gradient reads and output writes are HBM traffic)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="measure everything beyond the headline as well (without it, every --no-* option above is implied)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    args = p.parse_args()
+    if not args.full:       # a plain run: the headline line only
+        for k in ("no_cpu_baseline", "no_kernel_pass", "no_cache_tier", "no_laia", "no_config_c", "no_wide", "no_sweeps",
+                  "no_cold_tier"):
+            setattr(args, k, True)
+    return args
 
 
 def spawn_ranks(args):
@@ -146,6 +159,43 @@ def pmc_traffic(kernel_prefix):
             if name.startswith(kernel_prefix):
                 return v["hbm_bytes_per_launch"], os.path.relpath(f, ROOT)
     return None, None
+
+
+DUMP_ARRAY_BYTES = 32 << 20     # per array of rows with its float64 indices: the two pairs stay within 64 MB
+
+
+def _fit_rows(idx, width, seed):
+    """`idx`, or a fixed seeded sample of it (sorted) small enough that idx.size rows of `width` float32 and idx.size
+    float64 indices fit DUMP_ARRAY_BYTES."""
+    cap = max(1, DUMP_ARRAY_BYTES // (4 * width + 8))
+    if idx.size <= cap:
+        return idx
+    return np.sort(np.random.default_rng(seed).choice(idx, size=cap, replace=False))
+
+
+def dump_outputs(dirname, rows, table, applied_ids, id_offset=0, seed=2024):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 / float64 .npy files:
+        lookup_rows       the rows the step looked up ([positions, width]; its `out`)
+        lookup_positions  their positions in the batch
+        table_rows        the table after the step's SGD apply: every row the step updated + 4096 seeded random rows
+        table_row_ids     their row ids (global ids; `id_offset` = first row of the table given)
+    Rows and indices beyond DUMP_ARRAY_BYTES are a fixed, seeded sample of the positions / rows.  Same arguments, same
+    inputs: two builds are compared file by file."""
+    os.makedirs(dirname, exist_ok=True)
+    width = rows.shape[1]
+    pos = _fit_rows(np.arange(rows.shape[0], dtype=np.int64), width, seed)
+    upd = np.unique(applied_ids.astype(np.int64)) - id_offset
+    upd = upd[(upd >= 0) & (upd < table.shape[0])]          # (a shard holds only its own rows)
+    rnd = np.random.default_rng(seed).integers(0, table.shape[0], 4096)
+    ids = _fit_rows(np.union1d(upd, rnd), width, seed + 1)
+    arrays = {
+        "lookup_rows": rows[torch.from_numpy(pos).to(rows.device)].float().cpu().numpy(),
+        "lookup_positions": pos.astype(np.float64),
+        "table_rows": table[torch.from_numpy(ids).to(table.device)].float().cpu().numpy(),
+        "table_row_ids": (ids + id_offset).astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def init_table(rows, width, dev, seed=123):
@@ -715,7 +765,10 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=dev)
         from herald_amd import sharded_bench
-        return sharded_bench.run(args, rank, world, dev, cpu_baseline_fn=cpu_baseline)
+        dump_fn = None
+        if args.dump_outputs:
+            dump_fn = lambda rows, shard, applied, first: dump_outputs(args.dump_outputs, rows, shard, applied, id_offset=first)
+        return sharded_bench.run(args, rank, world, dev, cpu_baseline_fn=cpu_baseline, dump_fn=dump_fn)
 
     n = args.batch * args.fields
     one = args.launches == 1
@@ -978,6 +1031,11 @@ def main():
     total_ms = dev_ms if gate is not None else max(dev_ms, t_enq * 1e3)
     ms_per_step = total_ms / args.steps
     rows_per_s = n * args.steps / (total_ms * 1e-3)
+    if args.dump_outputs:
+        # before anything else touches the table or the buffers.  The last timed step applied batch b and looked up the
+        # rows of batch b + 1 (one-launch engines) / of batch b (two launches)
+        b = (K0 + wu + args.steps - 1) % nb
+        dump_outputs(args.dump_outputs, outs[((b + 1) % nb if one else b) % nbuf], table, ids_host[b])
 
     used = [(K0 + wu + k) % nb for k in range(args.steps)]
     u_mean = float(np.mean(uniq_counts[used]))

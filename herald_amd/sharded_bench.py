@@ -55,8 +55,10 @@ def _world1_same_path(args, rank, dev, emb, ids_dev, grads, n, lr, steps=300, wa
     return 1e3 * (time.perf_counter() - t0) / steps
 
 
-def _measure(args, rank, world, dev, batch, width, steps, warmup, per_kernel):
-    """One sharded workload: `steps` timed steps of bs=`batch`, d=`width` per GPU -> dict of what rank 0 reports."""
+def _measure(args, rank, world, dev, batch, width, steps, warmup, per_kernel, dump_fn=None):
+    """One sharded workload: `steps` timed steps of bs=`batch`, d=`width` per GPU -> dict of what rank 0 reports.
+    dump_fn(rows, shard, applied_ids, id_offset): called on rank 0 right after the timed steps with what the last one
+    computed (the rows it looked up, the rank's shard after its apply, the ids of the batch it applied)."""
     import os
     from herald_amd import ops, synth
     from herald_amd.sharded import FramedStep, ShardedEmbedding
@@ -147,6 +149,7 @@ def _measure(args, rank, world, dev, batch, width, steps, warmup, per_kernel):
             emb.push(None, grads[k % 2], lr, route=cur)          # backward: -lr scale, dedup-reduce, exchange, apply
             emb.complete(nxt)                                    # host counts + keys exchange of the next batch
             state["route"] = nxt
+            state["out"] = out
             return out
 
         native_steps = False
@@ -168,6 +171,9 @@ def _measure(args, rank, world, dev, batch, width, steps, warmup, per_kernel):
     t = torch.tensor([el], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
+    if dump_fn is not None and rank == 0:      # step k looked up and applied batch k
+        last = warmup + steps - 1
+        dump_fn(outs[last % 2] if framed else state["out"], emb.table, ids_host[last % nb], emb.starts[emb.rank])
     st = emb.stats
     xg = torch.tensor([st["xgmi_bytes_out"], st["xgmi_bytes_in"], st.get("xgmi_row_bytes_out", -1.0),
                        st.get("xgmi_useful_bytes_out", -1.0), st.get("owner_rows_max", 0)], dtype=torch.float64, device=dev)
@@ -274,8 +280,10 @@ def _pmc_traffic(batch, width):
     return out
 
 
-def run(args, rank, world, dev, cpu_baseline_fn=None):
-    main = _measure(args, rank, world, dev, args.batch, args.width, args.steps, args.warmup, per_kernel=True)
+def run(args, rank, world, dev, cpu_baseline_fn=None, dump_fn=None):
+    # per_kernel: the per-launch times (world size 1) and the same-path world-1 figure (N > 1) -- runs of their own, --full only
+    main = _measure(args, rank, world, dev, args.batch, args.width, args.steps, args.warmup,
+                    per_kernel=getattr(args, "full", True), dump_fn=dump_fn)
     # BASELINE configs[2] (wdl_criteo bs=4096 d=128 per GPU: the shape the reference's scaling table is quoted on) as a
     # second, shorter measurement in the same line -- never part of `value`
     second = None

@@ -23,7 +23,7 @@ def _run(extra_env, *args):
 
 
 def test_bench_n1_line_has_the_contract_fields(dev):
-    d = _run({}, "--rows", "1000000", "--steps", "256", "--warmup", "64", "--distinct-batches", "64",
+    d = _run({}, "--full", "--rows", "1000000", "--steps", "256", "--warmup", "64", "--distinct-batches", "64",
              "--cold-rows", "2000000")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -71,8 +71,29 @@ def test_bench_short_driver_run(dev):
     assert "hipGraph" in g["config"]["launch"]        # steps 5..24: the blocks [0, 16) and [16, 32) -> two replays
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(dev, tmp_path):
+    """A plain run (no --full) prints the headline line without any secondary figure; --dump-outputs writes what the last
+    timed step computed (float32 / float64, within 64 MB), and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    common = ("--rows", "1000000", "--steps", "40", "--warmup", "8", "--distinct-batches", "64")
+    lines = [_run({}, *common, "--dump-outputs", str(tmp_path / r)) for r in ("a", "b")]
+    for d in lines:
+        assert d["steps"] == 40 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+        for k in ("cpu_baseline", "cache_tier", "cold_tier", "laia_scheduler", "bit_exact_engine", "lookahead_sweep",
+                  "wide_bs1024_d512", "wide_bs4096_d128"):
+            assert k not in d, k
+    total = 0
+    for name in ("lookup_rows", "lookup_positions", "table_rows", "table_row_ids"):
+        a, b = (np.load(str(tmp_path / r / (name + ".npy"))) for r in ("a", "b"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    rows = np.load(str(tmp_path / "a" / "lookup_rows.npy"))
+    assert rows.shape == (lines[0]["config"]["ids_per_step"], 512) and np.isfinite(rows).all() and rows.any()
+
+
 def test_bench_two_launch_mode_still_reports_measured_kernel_times(dev):
-    d = _run({}, "--rows", "1000000", "--steps", "64", "--warmup", "32", "--distinct-batches", "64", "--launches", "2",
+    d = _run({}, "--full", "--rows", "1000000", "--steps", "64", "--warmup", "32", "--distinct-batches", "64", "--launches", "2",
              "--no-cache-tier", "--no-cpu-baseline", "--no-cold-tier", "--no-laia")
     assert d["config"]["launches_per_step"] == 2
     k = d["kernels"]
@@ -83,7 +104,7 @@ def test_bench_two_launch_mode_still_reports_measured_kernel_times(dev):
 def test_bench_sharded_leg_runs_on_nccl_at_world_size_1(dev):
     d = _run({"HA_FORCE_SHARDED": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29641", "RANK": "0",
               "WORLD_SIZE": "1", "LOCAL_RANK": "0"},
-             "--rows", "1000000", "--steps", "64", "--warmup", "16")
+             "--full", "--rows", "1000000", "--steps", "64", "--warmup", "16")
     assert d["n_gpus"] == 1 and d["steps"] == 64 and d["value"] > 0 and d["scaling"] == "weak"
     assert "sharded" in d["config"]["workload"] and "xgmi" in d
     assert d["ranks_seen"] == 1 and d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0

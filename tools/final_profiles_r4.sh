@@ -19,7 +19,7 @@ grep '^{' $O/stats.log | tail -1 > $O/summary/bench_under_rocprof.json
 cd $R
 mkdir -p profiles/r04 && cp $O/summary/pmc_traffic.json profiles/r04/pmc_traffic.json 2>/dev/null     # bench.py reads the newest profiles/r*/pmc_traffic.json
 # ---- bench lines on the final binaries ----
-python3 bench.py > $O/summary/bench_n1_default.json 2> $O/bench_n1_default.err
+python3 bench.py --full > $O/summary/bench_n1_default.json 2> $O/bench_n1_default.err
 python3 bench.py --steps 20 --warmup 5 > $O/summary/bench_n1_steps20_warmup5.json 2> /dev/null
 for i in 1 2 3; do python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline $B 2>/dev/null | python3 tools/ab_line.py driver_run short >> $O/summary/short_runs.txt; done
 HA_QSYNC=events python3 bench.py --no-cpu-baseline $B 2>/dev/null | python3 tools/ab_line.py events_sync long >> $O/summary/short_runs.txt
@@ -40,8 +40,8 @@ cd $R
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29633 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 HA_FORCE_SHARDED=1
 cd /tmp
 for sh in "256 512" "4096 128"; do set -- $sh
-  S="--batch $1 --width $2 --steps 64 --warmup 60 --no-cpu-baseline --no-config-c"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/sh_stats_$1 -- python3 $R/bench.py --batch $1 --width $2 --steps 300 --warmup 60 --no-cpu-baseline --no-config-c > $O/sh_stats_$1.log 2>&1
+  S="--full --batch $1 --width $2 --steps 64 --warmup 60 --no-cpu-baseline --no-config-c"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/sh_stats_$1 -- python3 $R/bench.py --full --batch $1 --width $2 --steps 300 --warmup 60 --no-cpu-baseline --no-config-c > $O/sh_stats_$1.log 2>&1
   mkdir -p $O/shp_$1
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/shp_$1/pmc_fetch -- python3 $R/bench.py $S > $O/shp_$1/pmc_fetch.log 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/shp_$1/pmc_write -- python3 $R/bench.py $S > $O/shp_$1/pmc_write.log 2>&1
@@ -58,8 +58,8 @@ if rows:
 PY
 done
 cd $R
-python3 bench.py --steps 500 --warmup 60 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/summary/bench_sharded_world1.json
-HA_SHARD_FIXED=1 python3 bench.py --steps 500 --warmup 60 --no-cpu-baseline --no-config-c 2>/dev/null | grep '^{' > $O/summary/bench_sharded_world1_fixed_frames.json
+python3 bench.py --full --steps 500 --warmup 60 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/summary/bench_sharded_world1.json
+HA_SHARD_FIXED=1 python3 bench.py --full --steps 500 --warmup 60 --no-cpu-baseline --no-config-c 2>/dev/null | grep '^{' > $O/summary/bench_sharded_world1_fixed_frames.json
 python3 tools/framed_hostprof.py 2>&1 | grep "us/step" > $O/summary/sharded_world1_host_vs_wall.txt
 unset HA_FORCE_SHARDED RANK WORLD_SIZE LOCAL_RANK
 # keep the merge-back small

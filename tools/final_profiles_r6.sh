@@ -34,7 +34,7 @@ for pol in LRU LFU LFUOpt; do
 done
 cd $R
 # ---- bench lines on the final binaries ----
-python3 bench.py > $O/summary/bench_n1_default.json 2> $O/bench_n1_default.err
+python3 bench.py --full > $O/summary/bench_n1_default.json 2> $O/bench_n1_default.err
 python3 bench.py --steps 20 --warmup 5 > $O/summary/bench_n1_steps20_warmup5.json 2> /dev/null
 for i in 1 2 3; do python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline $B 2>/dev/null | python3 tools/ab_line.py driver_run short >> $O/summary/short_runs.txt; done
 # ---- timeline + census of one apply launch; the wide path's step alone / beside its preparation ----
@@ -50,7 +50,7 @@ python3 $R/tools/laia_gaps.py $O/laia_stats > $O/summary/laia_gaps.txt 2>/dev/nu
 cd $R
 # ---- the sharded step at world size 1 (the N>1 code path on one GPU) ----
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29633 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 HA_FORCE_SHARDED=1
-python3 bench.py --steps 500 --warmup 60 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/summary/bench_sharded_world1.json
+python3 bench.py --full --steps 500 --warmup 60 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/summary/bench_sharded_world1.json
 unset HA_FORCE_SHARDED RANK WORLD_SIZE LOCAL_RANK
 find $O -name "*.csv" -size +3M -delete
 ls -la $O/summary
