@@ -27,7 +27,9 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      the sparse one as the tuple (ids, push plan); the rows come through the HET cache over the table
                      row-sharded across the ranks, EmbeddingLookUp_Gradient(enable_push_index=True) turns the plan into
                      IndexedSlices.push_indices and the communicate op pushes with embedding_update_with_push_keys;
-                     the dense tower's gradients are all-reduced (Hybrid).  torchrun for N > 1.
+                     the dense tower's gradients are all-reduced (Hybrid).  torchrun for N > 1.  With
+                     --cache-planned on one rank the cache runs its planned flow: the batch after next and its plan are
+                     booked ahead (LAIADataloader.peek_arr), every lookup and every push-plan update is one launch.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -118,10 +120,12 @@ def make_samples(nsamples, rows, seed=0):
 
 def train_laia(model="wdl", rows=200000, width=32, batch=64, steps=20, lr=0.01, cache="LRU", bound=0, cache_limit=None,
                seed=0, device="cuda:0", table_init=None, a2a=None, allreduce=None, local_shared=False, nsamples=None,
-               perf=False, log_every=0):
+               perf=False, log_every=0, cache_planned=False):
     """The laia-driven loop (run_laia.py:214-236).  `batch` = samples per worker and step; a2a / allreduce: optional
-    replacements of the collectives (several ranks on one GPU under gloo in the tests).  Returns (losses, embedding
-    parameter, tower, communicate op)."""
+    replacements of the collectives (several ranks on one GPU under gloo in the tests).  cache_planned (--cache-planned): on
+    one rank, the cache's planned flow -- the sparse loader hands the communicate op the (ids, push plan) of the batch after
+    next (`peek_arr`), its bookkeeping runs beside the step; the update pushes the plan's keys (no effect at world > 1).
+    Returns (losses, embedding parameter, tower, communicate op)."""
     import torch.distributed as dist
     from herald_amd import laia as hlaia
     dev = torch.device(device)
@@ -151,11 +155,17 @@ def train_laia(model="wdl", rows=200000, width=32, batch=64, steps=20, lr=0.01, 
     store = ShardedEmbedding(rows, width, dev, a2a=a2a)
     store.table.copy_(table_init[store.starts[store.rank]:store.starts[store.rank + 1]])
     param = hetu_ops.EmbeddingParameter(store=store)
+    planned = bool(cache_planned) and world == 1
     config = hetu_ops.Config(comm_mode="Hybrid", bsp=0, prefetch=True, cstable_policy=cache, cache_bound=bound,
-                             cache_limit=limit, cache_perf_enable=perf)
-    comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=sparse_dl.get_next_arr)
+                             cache_limit=limit, cache_perf_enable=perf, cache_plan_ahead=planned)
+    comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=sparse_dl.get_next_arr,
+                                                 peek_ids=sparse_dl.peek_arr if planned else None)
     barrier = dist.barrier if world > 1 else (lambda: None)
-    comm.forward_hook(config, first_ids=sparse_dl.get_next_arr(), barrier=barrier)
+    if planned:
+        # (the first batch is the one next_ids() returns now: peek_ids counts from it)
+        comm.forward_hook(config, barrier=barrier)
+    else:
+        comm.forward_hook(config, first_ids=sparse_dl.get_next_arr(), barrier=barrier)
     lookup = hetu_ops.EmbeddingLookUp(param, enable_push_index=True)
     lookup.forward_hook(config)
     lookup_grad = hetu_ops.EmbeddingLookUp_Gradient(param.shape, enable_push_index=True)
@@ -182,7 +192,7 @@ def train_laia(model="wdl", rows=200000, width=32, batch=64, steps=20, lr=0.01, 
                 p_.grad.div_(world)
         opt.step()
         grad = lookup_grad.compute(emb.grad, ids_plan)             # IndexedSlices(indices, values, push_indices = plan)
-        comm.compute(grad)              # -lr scale, embedding_update_with_push_keys, barrier, lookup of the next batch
+        comm.compute(grad)              # -lr scale, embedding_update_with_push_keys (planned: its planned form), barrier, next lookup
         losses.append(float(loss.detach()))
         if log_every and (k + 1) % log_every == 0 and rank == 0:
             print("step %d loss %.5f (%.1f ms/step)" % (k + 1, np.mean(losses[-log_every:]),
@@ -369,7 +379,9 @@ def main():
     ap.add_argument("--cache", default=None, help="cache policy: lru | lfu | lfuopt (with --comm PS / Hybrid)")
     ap.add_argument("--bound", type=int, default=100, help="cache bound")
     ap.add_argument("--cache-planned", action="store_true",
-                    help="--embedding cache at --bsp 0: the cache's planned flow (bookkeeping of the next batch beside this step)")
+                    help="--embedding cache at --bsp 0, or --laia: the cache's planned flow (bookkeeping of the next batch beside "
+                         "this step; --laia: the update pushes the batch's push plan).  With --laia at world size > 1 it is "
+                         "accepted and has no effect (the cache there talks to a remote store, call by call)")
     ap.add_argument("--nepoch", type=int, default=-1, help="epochs of `--steps` steps each (default: one)")
     ap.add_argument("--embedding", choices=["hbm", "step", "step3", "queue", "ps", "cache"], default=None,
                     help="this build's engine names; default: from --comm / --cache")
@@ -403,7 +415,7 @@ def main():
     if args.laia:
         losses = train_laia(args.model, args.rows, args.width, args.batch, args.steps, args.lr, args.cache, args.bound,
                             device="cuda:%d" % local_rank, local_shared=args.local_shared,
-                            log_every=max(1, args.steps // 10))[0]
+                            log_every=max(1, args.steps // 10), cache_planned=args.cache_planned)[0]
     else:
         losses = train(args.embedding, args.rows, args.width, args.batch, args.steps, args.lr, args.cache,
                        args.bound, cache_limit=cache_limit, device="cuda:%d" % local_rank,

@@ -421,7 +421,7 @@ class _CacheBase:
                   "ha_cache_sort_ahead_batch")
 
     # ---- the planned flow: the bookkeeping of a block of batches ahead, ONE launch per lookup / update ----------------------
-    def plan_block(self, keys_list, side=None):
+    def plan_block(self, keys_list, side=None, push_keys_list=None):
         """State that the device tensors of `keys_list` (1..16, one dtype, at most min(max_batch, 36,864) keys each) are the
         batches of the NEXT embedding_lookup_planned / embedding_update_planned pairs, in this order (ha_cache_plan_block,
         csrc/cache_block.hip: a local store; LRU: limit >= the batch; LFU / LFUOpt: every resident line updated since its lookup, as
@@ -430,9 +430,32 @@ class _CacheBase:
         `side` (default: a stream of the cache's own), beside whatever rows the cache's stream is still moving; every lookup and
         every update of these batches is then ONE launch.  Plan block b + 1 when block b starts (two blocks may be outstanding).
         Until the planned pairs are consumed the call-by-call methods raise; lines() / keys() / size() show the bookkeeping of
-        every planned batch (meaningful at the end of a block)."""
+        every planned batch (meaningful at the end of a block).
+
+        push_keys_list (optional, one entry per batch): the batch's update is embedding_update_with_push_keys (cache.cc:248-335)
+        with these push keys -- a sorted device tensor, float32 or (u)int64, at most max_batch keys, unchanged until the
+        bookkeeping has run (ha_cache_plan_block_push_keys) -- or, for a None entry, the bounded push of embedding_update.  The
+        planned lookups and updates are the same calls either way."""
         if self._remote is not None or not keys_list:
             raise ValueError("plan_block: a non-empty list of key tensors, local store")
+        pks = None
+        if push_keys_list is not None:
+            # (everything is checked before anything is enqueued)
+            if len(push_keys_list) != len(keys_list):
+                raise ValueError("plan_block: %d push-key entries for %d batches" % (len(push_keys_list), len(keys_list)))
+            pks = []
+            for pk in push_keys_list:
+                if pk is None:
+                    pks.append(None)
+                    continue
+                if not torch.is_tensor(pk) or not pk.is_cuda or pk.dtype not in (torch.float32, torch.int64, torch.uint64):
+                    raise ValueError("plan_block: push keys must be float32 or (u)int64 device tensors")
+                pk = pk.reshape(-1)
+                if not pk.is_contiguous():
+                    raise ValueError("plan_block: push keys are not contiguous")
+                if pk.numel() > self._max_batch:
+                    raise ValueError("plan_block: %d push keys (at most max_batch = %d)" % (pk.numel(), self._max_batch))
+                pks.append(pk)
         s = self._stream()
         if side is None:
             if getattr(self, "_plan_side", None) is None:
@@ -471,14 +494,25 @@ class _CacheBase:
             raise ValueError("plan_block: 1-16 key tensors of one dtype")
         ptrs = (ctypes.c_void_p * len(ks))(*[k.data_ptr() if k.numel() else None for k, _ in ks])
         ns = (ctypes.c_int64 * len(ks))(*[k.numel() for k, _ in ks])
+        pkinds = {0 if pk.dtype == torch.float32 else 1 for pk in (pks or []) if pk is not None}
+        if len(pkinds) > 1:
+            raise ValueError("plan_block: the push keys of a block share one dtype")
         self._ahead = None
         self._drop_ahead_ring()
         self._last_lookup = None
-        check(self._L.ha_cache_plan_block(self._h, ptrs, kinds.pop(), ns, len(ks), ctypes.c_void_p(side.cuda_stream),
-                                          ctypes.c_void_p(s.cuda_stream)), "ha_cache_plan_block")
+        if pks is None:
+            check(self._L.ha_cache_plan_block(self._h, ptrs, kinds.pop(), ns, len(ks), ctypes.c_void_p(side.cuda_stream),
+                                              ctypes.c_void_p(s.cuda_stream)), "ha_cache_plan_block")
+        else:
+            pptrs = (ctypes.c_void_p * len(ks))(*[pk.data_ptr() if pk is not None and pk.numel() else None for pk in pks])
+            pns = (ctypes.c_int64 * len(ks))(*[pk.numel() if pk is not None else -1 for pk in pks])
+            check(self._L.ha_cache_plan_block_push_keys(self._h, ptrs, kinds.pop(), ns, pptrs, pkinds.pop() if pkinds else 0, pns,
+                                                        len(ks), ctypes.c_void_p(side.cuda_stream),
+                                                        ctypes.c_void_p(s.cuda_stream)), "ha_cache_plan_block_push_keys")
         if not hasattr(self, "_planned"):
             self._planned = []
-        self._planned.extend([k, False] for k, _ in ks)      # [key tensor (kept alive), its lookup done?]
+        # [key tensor (kept alive), its lookup done?, push-key tensor (kept alive) or None]
+        self._planned.extend([k, False, pks[j] if pks is not None else None] for j, (k, _) in enumerate(ks))
 
     def plan_pending(self):
         """Planned calls (lookups + updates) still to be made."""
@@ -826,8 +860,8 @@ class CacheSparseTable:
 
     # the planned flow (csrc/cache_block.hip): the ids of a block of batches a block early -- bookkeeping ahead on a side stream,
     # ONE launch per lookup and per update
-    def plan_block(self, keys_list, side=None):
-        self.cache.plan_block([k[0] if isinstance(k, tuple) else k for k in keys_list], side)
+    def plan_block(self, keys_list, side=None, push_keys_list=None):
+        self.cache.plan_block([k[0] if isinstance(k, tuple) else k for k in keys_list], side, push_keys_list)
 
     def embedding_lookup_planned(self, dest, sync=False):
         w = self.cache.embedding_lookup_planned(dest)

@@ -80,6 +80,10 @@ struct BookArgs {
     PlanRec *rec;            // [count]
     unsigned long long *xw;  // [4][kBookWg] exchange words
     long long nmax;
+    // per batch: nullptr = BOUND mode (a line is pushed when its counter exceeds push_bound, cache.cc:159); else PUSH-KEY mode
+    // (cache.cc:295-299): pk_mark[i][u] = 1 when unique key u is one of the batch's push keys (cache_plan_push_mark_kernel),
+    // and a line is pushed iff it is marked and holds data
+    const uint8_t *pk_mark[kPlanBlockMax];
 };
 // a line record's word 3 = freq | state << 32 | hg << 40
 __device__ __forceinline__ unsigned long long line_w3(uint8_t state, bool hg) {
@@ -149,7 +153,8 @@ __device__ __forceinline__ uint32_t book_rank(bool f, uint32_t *s_w4, uint32_t *
 //   LRUCache::insert (lru_cache.cc:9-25) evicts while size > limit: the first size + M - limit VALID entries from the log head
 //   (valid: the line is resident and still carries the entry's stamp); their slots go back on the stack, the dirty ones
 //   (updates != 0) are listed for the batch's update to push (cache.cc:160-166: the pending evictions join every push);
-//   updates += occurrences; a line whose counter exceeds push_bound is pushed and starts again at 0 (cache.cc:159,171-177).
+//   updates += occurrences; a line whose counter exceeds push_bound is pushed and starts again at 0 (cache.cc:159,171-177);
+//   a batch planned with push keys pushes the lines whose key is marked instead (cache.cc:295-299; BookArgs::pk_mark).
 __global__ __launch_bounds__(kBookThreads) void cache_book_block_kernel(Cache c, BookArgs a) {
     __shared__ uint32_t s_a[kBookWg], s_b[kBookWg], s_w4[kBookThreads / 64];
     __shared__ int s_abort;
@@ -178,6 +183,7 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_block_kernel(Cache c,
         const int U = static_cast<int>(a.hdr[i]->n_unique);
         const uint32_t *uniq = a.uniq[i];
         const int32_t *counts = a.counts[i];
+        const uint8_t *pkm = a.pk_mark[i];      // (every line of the batch that the update finds holds data)
         // ---- log nearly full: compact it first (valid entries keep their order), a tile of kBookWg x 256 entries at a time
         if (tail - head > c.Lcap - 4 * c.nmax - 2048 - kBookWg * kBookThreads) {
             long long wr = head;
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_block_kernel(Cache c,
                 const unsigned long long w3 = ldc(line_word(c.line, s, 3));
                 const bool hg = ((w3 >> 40) & 1ull) != 0ull;
                 const int upd = static_cast<int>(w2 >> 32) + counts[u];
-                const bool push = upd > c.push_bound;
+                const bool push = pkm ? pkm[u] != 0 : upd > c.push_bound;
                 const unsigned long long st = static_cast<unsigned long long>(clock + u);
                 stc(line_word(c.line, s, 0), st);
                 stc(line_word(c.line, s, 2), static_cast<unsigned long long>(kk[j]) |
@@ -275,7 +281,7 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_block_kernel(Cache c,
                 const long long fi = ftop - 1 - static_cast<long long>(mb + rk[j]);
                 const int s = fi >= 0 ? ldc(c.free_list + fi) : 0;     // (running out of slots: sizing, checked on the host)
                 const int upd = counts[u];
-                const bool push = upd > c.push_bound;
+                const bool push = pkm ? pkm[u] != 0 : upd > c.push_bound;
                 const unsigned long long st = static_cast<unsigned long long>(clock + u);
                 stc(line_word(c.line, s, 0), st);
                 stc(line_word(c.line, s, 2), static_cast<unsigned long long>(kk[j]) |
@@ -623,6 +629,7 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_lfu_kernel(Cache c, B
         const int U = static_cast<int>(a.hdr[i]->n_unique);
         const uint32_t *uniq = a.uniq[i];
         const int32_t *counts = a.counts[i];
+        const uint8_t *pkm = a.pk_mark[i];      // (every line of the batch that the update finds holds data)
         const int per = (U + kBookWg - 1) / kBookWg;
         const int u0 = min(g * per, U), u1 = min(u0 + per, U);
         // ---- phase 1: probe; what the two touches will make of every line found ---------------------------------------------
@@ -754,13 +761,15 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_lfu_kernel(Cache c, B
                     // this line is the one the batch's first insert evicts: the lookup still reads it (slot vh_slot of the
                     // record), the update does not find it -- a line without data in a spare slot, pushed at once
                     a.it_slot[at + u] = ldc(c.free_list + (ftop - M - 1));
-                    a.it_flag[at + u] = static_cast<uint8_t>(kPosTemp | kPosPush | kPosVictim | (hg ? kPosVictimHg : 0) |
-                                                             (vdirty ? kPosVictimPush : 0));
+                    // (push-key mode: a line without data is not pushed -- its gradient is dropped, cache.cc:295-299; the
+                    // evicted line itself is still pushed as an eviction, kPosVictimPush)
+                    a.it_flag[at + u] = static_cast<uint8_t>(kPosTemp | (pkm ? 0 : kPosPush) | kPosVictim |
+                                                             (hg ? kPosVictimHg : 0) | (vdirty ? kPosVictimPush : 0));
                     a.it_upd[at + u] = counts[u];
                     continue;
                 }
                 const int upd = static_cast<int>(w2[j] >> 32) + counts[u];
-                const bool push = upd > c.push_bound;
+                const bool push = pkm ? pkm[u] != 0 : upd > c.push_bound;
                 uint8_t ns = state;
                 uint32_t f2 = f;
                 if (state == kResident) {
@@ -788,11 +797,11 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_lfu_kernel(Cache c, B
                 const int upd = counts[u];
                 if (q < v_new) {          // inserted and evicted again by a later insert (or dropped): see the header
                     a.it_slot[at + u] = s;
-                    a.it_flag[at + u] = static_cast<uint8_t>(kPosMiss | kPosTemp | kPosPush);
+                    a.it_flag[at + u] = static_cast<uint8_t>(kPosMiss | kPosTemp | (pkm ? 0 : kPosPush));
                     a.it_upd[at + u] = upd;
                     continue;
                 }
-                const bool push = upd > c.push_bound;
+                const bool push = pkm ? pkm[u] != 0 : upd > c.push_bound;
                 const unsigned long long st = static_cast<unsigned long long>(clock2 + u);
                 stc(line_word(c.line, s, 0), st);
                 stc(line_word(c.line, s, 2), static_cast<unsigned long long>(kk[j]) |
@@ -836,6 +845,7 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_lfu_kernel(Cache c, B
             r.umiss = v_new + (scan && vin ? 1 : 0);
             r.vh_slot = scan && vin ? vslot : -1;
             r.vh_upd = scan && vin ? vupd : 0;
+            r.vh_key = scan && vin ? vkey : 0;
             a.rec[i] = r;
         }
         // ---- the batch is booked: the next one probes what this one left; the blocks of the rewritten keys ---------------------
@@ -865,6 +875,45 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_lfu_kernel(Cache c, B
         ctl->U = 0;
         ctl->M = 0;
     }
+}
+
+// ---- the push keys of a push-key batch (side stream, behind the index plans, in front of the bookkeeping launch) -----------
+// A thread per push key: the key as the call-by-call update reads it (cache_f32_to_u32_kernel / cache_u64_to_u32_kernel), its
+// position among the batch's sorted unique keys by binary search, a mark there.  The bookkeeping launch then reads one byte
+// per key instead of searching itself (its launch is serial per batch; the search is ~13 dependent loads per key).  Push keys
+// that are not keys of the batch mark nothing (cache.cc:295-299 skips them); duplicates mark the same byte.
+struct PushMarkArgs {
+    const void *keys[kPlanBlockMax];     // nullptr: no push keys (a bound-mode batch, an empty push set or an empty batch)
+    long long n[kPlanBlockMax];
+    const PlanHeader *hdr[kPlanBlockMax];
+    const uint32_t *uniq[kPlanBlockMax];
+    int nb[kPlanBlockMax];               // keys of the batch (U <= nb)
+    int kind;                            // 0: float32 push keys, 1: 64-bit integers
+};
+__global__ __launch_bounds__(256) void cache_plan_push_mark_kernel(PushMarkArgs m, uint8_t *mark, long long nmax) {
+    const int i = blockIdx.y;
+    const long long j = blockIdx.x * 256ll + threadIdx.x;
+    if (m.keys[i] == nullptr || j >= m.n[i])
+        return;
+    uint32_t k;
+    if (m.kind == 0) {
+        k = f32_to_key(static_cast<const float *>(m.keys[i])[j]);
+    } else {
+        const uint64_t v = static_cast<const uint64_t *>(m.keys[i])[j];
+        k = v > 0xFFFFFFFEull ? 0xFFFFFFFEu : static_cast<uint32_t>(v);
+    }
+    const int U = min(static_cast<int>(m.hdr[i]->n_unique), m.nb[i]);
+    const uint32_t *uq = m.uniq[i];
+    int lo = 0, hi = U;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (uq[mid] < k)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    if (lo < U && uq[lo] == k)
+        mark[static_cast<long long>(i) * nmax + lo] = 1;
 }
 
 // ---- the items per sorted position (side stream, behind the bookkeeping launch) --------------------------------------------
@@ -995,20 +1044,25 @@ __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
 
 // ---- the update of a planned batch: ONE launch -----------------------------------------------------------------------------
 // the first kPlanMetaBlocks workgroups: a thread per sorted position, the heads work: the line's version (staged by the
-//     lookup, + updates for a pushed line: cache.cc:171-177), the store's version of a pushed line, hasgrad;
+//     lookup, + updates for a pushed line: cache.cc:171-177; for EVERY line of a push-key batch: cache.cc:321-327), the store's
+//     version of a pushed line, hasgrad;
 // the next kPlanEvictBlocks workgroups: a wave per evicted dirty line: store row += its gradient, store version += its updates
 //     (PSFhandle_embedding.cc:23-27); the slot is free already (the bookkeeping freed it, nothing reuses it before the next
 //     batch's lookup);
 // the rest: the ordered accumulate (apply_body, DUAL == 2: gradient buffer and data row; pushed lines take the push epilogue --
 //     store row += the line's new gradient, gradient buffer = 0).
 // (The independent short roles come first in the grid: they start with the launch, not behind 400 accumulate workgroups.)
+// pkmode (a batch planned with push keys): a line without data (kPosTemp) carries no kPosPush, so its accumulate keeps the
+// gradient in the spare slot instead of pushing it -- the gradient the reference drops.  Nothing reads it again: the slot stays
+// on the free stack, and every line that takes a slot next is a miss (no kPosInit: its accumulate starts from 0, its lookup
+// adds no gradient) or, call by call, an insert that clears hasgrad.
 constexpr int kPlanEvictBlocks = 64, kPlanMetaBlocks = 8;
 template <int VEC>
 __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
     Cache c, const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm, int n, const float *__restrict__ grads,
     ApplyMaps maps, const int32_t *__restrict__ it_upd_pos, const long long *__restrict__ pver,
     const int32_t *__restrict__ ev_slot, const uint32_t *__restrict__ ev_key, const int32_t *__restrict__ ev_upd,
-    const PlanRec *__restrict__ rec) {
+    const PlanRec *__restrict__ rec, int pkmode) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
     const int b = blockIdx.x;
     if (b >= kPlanMetaBlocks + kPlanEvictBlocks) {
@@ -1019,9 +1073,13 @@ __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
     const int lane = lane_id();
     if (b >= kPlanMetaBlocks) {
         const int E = static_cast<int>(min(rec->E, static_cast<long long>(n)));
-        for (int j = (b - kPlanMetaBlocks) * 16 + static_cast<int>(threadIdx.x >> 6); j < E; j += kPlanEvictBlocks * 16) {
-            const int s = uniform(ev_slot[j]);
-            const long long lk = static_cast<long long>(uniform(ev_key[j]));
+        // push-key mode, LFU policies: the dirty line the batch's own lookup evicted is pushed by a wave of its own (its key's
+        // item is a line without data, not pushed, whose accumulate has no push epilogue to carry it); its version: meta role
+        const int EV = E + ((pkmode && rec->vh_slot >= 0 && rec->vh_upd != 0) ? 1 : 0);
+        for (int j = (b - kPlanMetaBlocks) * 16 + static_cast<int>(threadIdx.x >> 6); j < EV; j += kPlanEvictBlocks * 16) {
+            const bool vic = j == E;
+            const int s = uniform(vic ? static_cast<int>(rec->vh_slot) : ev_slot[j]);
+            const long long lk = static_cast<long long>(uniform(vic ? static_cast<uint32_t>(rec->vh_key) : ev_key[j]));
             if (s < 0 || s >= c.S || lk >= c.store_rows)
                 continue;
             float *row = c.table + lk * c.width;
@@ -1050,7 +1108,7 @@ __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
                 for (long long q = lane; q < c.width; q += kWave)
                     row[q] = __fadd_rn(row[q], g[q]);
             }
-            if (lane == 0)
+            if (lane == 0 && !vic)
                 c.srv_ver[lk] += ev_upd[j];
         }
         return;
@@ -1059,17 +1117,20 @@ __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
         const int4 it = maps.pos_item[p];
         if (it.x < 0 || !(it.z & kPosHead) || it.x >= c.S || static_cast<long long>(static_cast<uint32_t>(it.y)) >= c.store_rows)
             continue;
-        if (it.z & kPosTemp) {     // (LFU policies) a line that is not in the cache: pushed, nothing of it stays
-            c.srv_ver[static_cast<uint32_t>(it.y)] += it_upd_pos[p] + ((it.z & kPosVictimPush) ? static_cast<int>(rec->vh_upd) : 0);
+        if (it.z & kPosTemp) {     // (LFU policies) a line that is not in the cache: pushed (push-key mode: dropped), nothing of it stays
+            c.srv_ver[static_cast<uint32_t>(it.y)] += (pkmode ? 0 : it_upd_pos[p]) +
+                                                      ((it.z & kPosVictimPush) ? static_cast<int>(rec->vh_upd) : 0);
             continue;
         }
         const int s = it.x;
         const long long pv = pver[p];
         long long v = pv != kVerKeep ? pv : c.line[s].version;
+        const int upd = it_upd_pos[p];
         if (it.z & kPosPush) {
-            const int upd = it_upd_pos[p];
             v += upd;
             c.srv_ver[static_cast<uint32_t>(it.y)] += upd;
+        } else if (pkmode) {       // cache.cc:321-327: every line's version goes up by its counter, pushed or not
+            v += upd;
         }
         c.line[s].version = v;
         c.hasgrad[s] = 1;
@@ -1135,6 +1196,7 @@ static int plan_slot_alloc(ha_cache *h, PlanSlot &sl) {
     PLAN_ALLOC(ev_key, all);
     PLAN_ALLOC(ev_upd, all);
     PLAN_ALLOC(rec, kPlanBlockMax);
+    PLAN_ALLOC(pk_mark, all);
 #undef PLAN_ALLOC
     for (int i = 0; ok && i < kPlanBlockMax; ++i) {
         char *p = nullptr;
@@ -1167,11 +1229,20 @@ extern "C" int ha_cache_plan_pending(ha_cache *h) {
 // bookkeeping: the row launches of the block that used this block's buffers before, or call-by-call entry points).  At most TWO
 // blocks are outstanding (the one being consumed and the next).  The key buffers must stay unchanged until the bookkeeping
 // has run (event `booked`; the row launches wait for it).
-extern "C" int ha_cache_plan_block(ha_cache *h, const void *const *keys, int key_kind, const int64_t *n, int count,
-                                   ha_stream_t side, ha_stream_t main) {
+// push_keys == nullptr: every batch in bound mode (ha_cache_plan_block); else ha_cache_plan_block_push_keys (see the header).
+static int plan_block_impl(ha_cache *h, const void *const *keys, int key_kind, const int64_t *n, const void *const *push_keys,
+                           int push_kind, const int64_t *n_push, int count, ha_stream_t side, ha_stream_t main) {
     HA_REQUIRE(h && keys && n && (key_kind == 0 || key_kind == 1) && count >= 1 && count <= kPlanBlockMax,
                "cache_plan_block: bad arguments (1..%d batches)", kPlanBlockMax);
     Cache &c = h->c;
+    const bool with_pk = push_keys != nullptr;
+    if (with_pk) {
+        HA_REQUIRE(n_push && (push_kind == 0 || push_kind == 1), "cache_plan_block_push_keys: bad arguments (push_kind 0 or 1)");
+        for (int i = 0; i < count; ++i)
+            HA_REQUIRE(n_push[i] <= c.nmax && (n_push[i] <= 0 || push_keys[i]),
+                       "cache_plan_block_push_keys: batch %d has %ld push keys (at most max_batch = %ld)", i, (long)n_push[i],
+                       (long)c.nmax);
+    }
     HA_REQUIRE(c.table && !c.remote && !c.bypass, "cache_plan_block: a cache over a local store, not bypassed");
     HA_REQUIRE(c.row_start == 0 && c.store_rows >= c.length, "cache_plan_block: the store must hold every key of the cache's range");
 
@@ -1227,7 +1298,14 @@ extern "C" int ha_cache_plan_block(ha_cache *h, const void *const *keys, int key
         }
     }
     if (ss != ms) {
-        if (sl.rows_recorded && h->last_planned_type >= 0) {
+        if (with_pk) {
+            // push keys (and ids) are often written on `main` just before this call (the laia loader's gather): ALWAYS order
+            // behind everything enqueued there so far, not only behind the rows of the block that used this slot before
+            if (sl.rows_recorded)
+                HA_CHECK_HIP(hipStreamWaitEvent(ss, sl.rows_done, 0));
+            HA_CHECK_HIP(hipEventRecord(h->plan_fork, ms));
+            HA_CHECK_HIP(hipStreamWaitEvent(ss, h->plan_fork, 0));
+        } else if (sl.rows_recorded && h->last_planned_type >= 0) {
             // the planned flow goes on: this slot's buffers were last read by the rows of the block two before the one being
             // consumed -- nothing else of the row stream concerns the bookkeeping (it owns the control fields, the rows the
             // data fields), and this event is long complete: no barrier parked on the planning stream's queue
@@ -1249,6 +1327,10 @@ extern "C" int ha_cache_plan_block(ha_cache *h, const void *const *keys, int key
     BookArgs a;
     memset(&a, 0, sizeof(a));
     a.count = count;
+    PushMarkArgs pm;
+    memset(&pm, 0, sizeof(pm));
+    pm.kind = push_kind;
+    long long np_max = 0, z0 = -1, z1 = 0;      // the marks to clear: [z0, z1) of pk_mark (one fill for the block)
     for (int i = 0; i < count; ++i) {
         PlanPtrs p = plan_layout(sl.ws[i], n[i]);
         a.n[i] = static_cast<int>(n[i]);
@@ -1256,7 +1338,29 @@ extern "C" int ha_cache_plan_block(ha_cache *h, const void *const *keys, int key
         a.uniq[i] = p.uniq;
         a.counts[i] = p.counts;
         sl.n[i] = n[i];
+        sl.pk[i] = with_pk && n_push[i] >= 0;
+        if (sl.pk[i]) {
+            uint8_t *mark = sl.pk_mark + static_cast<long long>(i) * c.nmax;
+            a.pk_mark[i] = mark;
+            if (n[i] > 0) {
+                z0 = z0 < 0 ? static_cast<long long>(i) * c.nmax : z0;
+                z1 = static_cast<long long>(i) * c.nmax + n[i];
+                if (n_push[i] > 0) {
+                    pm.keys[i] = push_keys[i];
+                    pm.n[i] = n_push[i];
+                    pm.hdr[i] = p.hdr;
+                    pm.uniq[i] = p.uniq;
+                    pm.nb[i] = static_cast<int>(n[i]);
+                    np_max = n_push[i] > np_max ? n_push[i] : np_max;
+                }
+            }
+        }
     }
+    if (z0 >= 0)
+        HA_CHECK_HIP(hipMemsetAsync(sl.pk_mark + z0, 0, static_cast<size_t>(z1 - z0), ss));
+    if (np_max > 0)
+        hipLaunchKernelGGL(cache_plan_push_mark_kernel, dim3(static_cast<unsigned>((np_max + 255) / 256), count), dim3(256), 0, ss,
+                           pm, sl.pk_mark, (long long)c.nmax);
     a.it_slot = sl.it_slot; a.it_flag = sl.it_flag; a.it_upd = sl.it_upd;
     a.ev_slot = sl.ev_slot; a.ev_key = sl.ev_key; a.ev_upd = sl.ev_upd;
     a.rec = sl.rec;
@@ -1296,6 +1400,18 @@ extern "C" int ha_cache_plan_block(ha_cache *h, const void *const *keys, int key
     h->same_fast = false;
     h->ring_count = h->ring_head = 0;
     return 0;
+}
+
+extern "C" int ha_cache_plan_block(ha_cache *h, const void *const *keys, int key_kind, const int64_t *n, int count,
+                                   ha_stream_t side, ha_stream_t main) {
+    return plan_block_impl(h, keys, key_kind, n, nullptr, 0, nullptr, count, side, main);
+}
+
+extern "C" int ha_cache_plan_block_push_keys(ha_cache *h, const void *const *keys, int key_kind, const int64_t *n,
+                                             const void *const *push_keys, int push_kind, const int64_t *n_push, int count,
+                                             ha_stream_t side, ha_stream_t main) {
+    HA_REQUIRE(push_keys && n_push, "cache_plan_block_push_keys: push_keys and n_push are required");
+    return plan_block_impl(h, keys, key_kind, n, push_keys, push_kind, n_push, count, side, main);
 }
 
 // the slot and batch index of the next planned call of `type` (0 lookup, 1 update)
@@ -1375,11 +1491,11 @@ extern "C" int ha_cache_update_planned(ha_cache *h, int64_t n, const float *grad
         if (vec_ok)
             hipLaunchKernelGGL(cache_update_planned_kernel<4>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
                                grads, maps, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at, sl->ev_key + at, sl->ev_upd + at,
-                               sl->rec + i);
+                               sl->rec + i, sl->pk[i] ? 1 : 0);
         else
             hipLaunchKernelGGL(cache_update_planned_kernel<1>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
                                grads, maps, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at, sl->ev_key + at, sl->ev_upd + at,
-                               sl->rec + i);
+                               sl->rec + i, sl->pk[i] ? 1 : 0);
         HA_LAUNCH_CHECK();
     }
     cache_mark(h, kTEnd, s);

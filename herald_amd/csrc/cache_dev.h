@@ -124,8 +124,8 @@ struct PlanRec {
     // the LFU policies (LRU: erep = E, umiss = 0, vh_slot = -1): erep = dirty lines the lookup evicted (the perf dict's
     // num_evict; E counts those of them the update pushes by a wave of their own), umiss = keys the update does not find in
     // the cache (num_miss of the Push record), vh_* = the evicted line when it is a line of the batch itself (slot, update
-    // counter; its key's record carries kPosVictim)
-    long long erep, umiss, vh_slot, vh_upd;
+    // counter, key; its key's record carries kPosVictim)
+    long long erep, umiss, vh_slot, vh_upd, vh_key;
 };
 // the buffers of one planned block (two exist: the block being consumed and the next)
 struct PlanSlot {
@@ -140,7 +140,9 @@ struct PlanSlot {
     uint32_t *ev_key = nullptr;
     int32_t *ev_upd = nullptr;
     PlanRec *rec = nullptr;             // [kPlanBlockMax]
+    uint8_t *pk_mark = nullptr;         // [kPlanBlockMax][nmax] push-key batches: 1 = unique key u is one of the batch's push keys
     int64_t n[kPlanBlockMax] = {};
+    bool pk[kPlanBlockMax] = {};        // batch i was planned with push keys (ha_cache_plan_block_push_keys), else bound mode
     int count = 0;                      // batches of the block (0: the slot was never used)
     int next_call = 0;                  // 2 i = the lookup of batch i is due, 2 i + 1 = its update; 2 count = consumed
     bool waited = false;                // the row stream already waits for `booked`

@@ -131,7 +131,7 @@ class ParameterServerCommunicateOp:
         self.next_ids = next_ids
         self.peek_ids = peek_ids
         self._peek_offset = 1
-        self._planned = None          # the planned flow: ids tensors of the planned batches, oldest first
+        self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
 
     def forward_hook(self, config, first_ids=None, barrier=lambda: None):   # :130-242
         self.config, self.barrier = config, barrier
@@ -186,10 +186,12 @@ class ParameterServerCommunicateOp:
                 self.compute = self._compute_no_prefetch
         if config.prefetch:                                            # first prefetch (:168-176, 196-205)
             ids = first_ids if first_ids is not None else self.next_ids()
-            if isinstance(ids, tuple):          # a laia data loader hands over (ids, push plan): cstable.py:49
-                ids = ids[0]
-            self.sparse_pull_val = torch.empty(tuple(ids.shape) + (p.shape[1],), dtype=torch.float32,
-                                               device=ids.device)
+            # a laia data loader hands over (ids, push plan): cstable.py:49 (the planned flow plans the batch with its plan)
+            first = ids[0] if isinstance(ids, tuple) else ids
+            self.sparse_pull_val = torch.empty(tuple(first.shape) + (p.shape[1],), dtype=torch.float32,
+                                               device=first.device)
+            if self._planned is None:
+                ids = first
             # (peek_ids counts from the batch next_ids() returns: an explicit first batch is the one before it)
             self._peek_offset = 0 if first_ids is not None else 1
             config.ps_map[p] = (self._pull(ids), self.sparse_pull_val)
@@ -235,11 +237,13 @@ class ParameterServerCommunicateOp:
         vals = grad.values.reshape(-1, self.parameter.shape[1])
         if self._planned is not None:
             idx = grad.indices.reshape(-1)
-            if grad.push_indices is not None or not self._planned or not _same_tensor(self._planned[0], idx):
+            pk = grad.push_indices.reshape(-1) if grad.push_indices is not None else None
+            if not self._planned or not _same_tensor(self._planned[0][0], idx) or (pk is None) != (self._planned[0][1] is None) \
+                    or (pk is not None and not _same_tensor(self._planned[0][1], pk)):
                 raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead): the gradients pushed are not those of the "
-                                   "batch pulled last")
+                                   "batch pulled last, or not with the push plan it was planned with")
             self._planned.pop(0)
-            return self.cache.embedding_update_planned(vals)
+            return self.cache.embedding_update_planned(vals)     # (a planned plan: cache.cc:248-335, _embeddingUpdateWithPushKeys)
         if grad.push_indices is None:
             # The executor pushes the gradients of the batch it looked up last (bsp / ssp: push(k) follows pull(k) as the
             # cache's next operation, ParameterServerCommunicate.py:41-56) and does not write the ids in between: when the
@@ -248,24 +252,34 @@ class ParameterServerCommunicateOp:
             return self.cache.embedding_update(idx, vals, same_as_lookup=self.cache.looked_up_last(idx))
         return self.cache.embedding_update_with_push_keys(grad.indices.reshape(-1), grad.push_indices.reshape(-1), vals)
 
+    def _plan(self, batch):
+        """Plan one batch: ids alone (the bounded push), or (ids, push plan) of a laia-scheduled batch (its update pushes the
+        plan's keys, cache.cc:248-335)."""
+        if isinstance(batch, tuple):
+            ids, plan = batch[0].reshape(-1), batch[1].reshape(-1)
+            self.cache.plan_block([ids], push_keys_list=[plan])
+        else:
+            ids, plan = batch.reshape(-1), None
+            self.cache.plan_block([ids])
+        self._planned.append((ids, plan))
+
     def _pull_cache(self, ids):
-        if isinstance(ids, tuple):              # (ids, push plan) of a laia-scheduled batch (cstable.py:49)
-            ids = ids[0]
         dest = self.sparse_pull_val.reshape(-1, self.parameter.shape[1])
         if self._planned is not None:
-            flat = ids.reshape(-1)
             if not self._planned:                                  # the first pull: nothing planned yet
-                self.cache.plan_block([flat])
-                self._planned.append(flat)
-            if len(self._planned) != 1 or not _same_tensor(self._planned[0], flat):
+                self._plan(ids)
+            flat = (ids[0] if isinstance(ids, tuple) else ids).reshape(-1)
+            plan = ids[1].reshape(-1) if isinstance(ids, tuple) else None
+            if len(self._planned) != 1 or not _same_tensor(self._planned[0][0], flat) or \
+                    (plan is None) != (self._planned[0][1] is None) or (plan is not None and not _same_tensor(self._planned[0][1], plan)):
                 raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead): pulls and pushes must alternate, batch "
                                    "after batch, on the tensors the loader handed out")
             nxt = self.peek_ids(self._peek_offset)                 # the batch after this one: its bookkeeping runs from now on,
             if nxt is not None:                                    # beside this batch's rows and the model's step
-                nxt = (nxt[0] if isinstance(nxt, tuple) else nxt).reshape(-1)
-                self.cache.plan_block([nxt])
-                self._planned.append(nxt)
+                self._plan(nxt)
             return self.cache.embedding_lookup_planned(dest)      # (no next batch: the next pull plans for itself)
+        if isinstance(ids, tuple):              # (ids, push plan) of a laia-scheduled batch (cstable.py:49)
+            ids = ids[0]
         return self.cache.embedding_lookup(ids.reshape(-1), dest)
 
     def _push_pull_cache(self, grad):

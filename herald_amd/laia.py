@@ -482,6 +482,7 @@ class LAIADataloader:
         self.is_sparse = is_sparse
         self.device = device
         self._raw_dev = None
+        self._made = {}          # absolute batch position -> what _get_arr made of it (one set of tensors per batch)
 
     def init_states(self, rank=None, nrank=None):
         if nrank is None:
@@ -491,6 +492,7 @@ class LAIADataloader:
         self.batch_size = self.sched.batch_size
         self.batch_index = 0
         self.rank = rank
+        self._made = {}
         if self.device is not None:
             import torch
             self._raw_dev = torch.from_numpy(self.raw_data).to(self.device)
@@ -501,25 +503,52 @@ class LAIADataloader:
         import torch
         return self._raw_dev[torch.as_tensor(np.asarray(idx, dtype=np.int64), device=self.device)]
 
-    def _get_arr(self, batchind):
-        idx = self.sched.get_input_index_array(self.batch_index)
+    def _make(self, batchind):
+        idx = self.sched.get_input_index_array(batchind)
         if not self.is_sparse:
             return self._rows(idx)
-        plan = self.sched.get_comm_plan_array(self.batch_index).astype(np.float32)
+        plan = self.sched.get_comm_plan_array(batchind).astype(np.float32)
         if self._raw_dev is not None:
             import torch
             plan = torch.from_numpy(plan).to(self.device)
         return (self._rows(idx), plan)
 
+    def _position(self):
+        """Batches this loader has consumed (the scheduler's count of them)."""
+        return self.sched._cursor[self.sched_id]
+
+    def _get_arr(self, j=0):
+        """Batch j after the current one, made once: get_next_arr, peek_arr and get_arr hand out the same tensors for a batch
+        (a consumer may recognise a batch by its tensors, as the planned cache flow does)."""
+        pos = self._position() + j
+        res = self._made.get(pos)
+        if res is None:
+            res = self._made[pos] = self._make((self.batch_index + j) % self.batch_num)
+        return res
+
     def get_arr(self):
         """The current batch; steps the scheduler's queue forward (laia_dataloader.py:201-206)."""
-        res = self._get_arr(self.batch_index)
+        res = self._get_arr()
+        self._made.pop(self._position(), None)
         self.batch_index = (self.batch_index + 1) % self.batch_num
         self.sched.step_forward(self.sched_id)
         return res
 
     def get_next_arr(self):
-        return self._get_arr(self.batch_index)
+        return self._get_arr()
+
+    def peek_arr(self, j):
+        """What get_next_arr will return j batches from now (peek_arr(0) = get_next_arr()), or None when the scheduler's window
+        does not hold that batch yet.  Never blocks, never steps the window."""
+        sched = self.sched
+        pos = self._position() + int(j)
+        if j < 0 or pos in self._made:
+            return self._made.get(pos)
+        if not (sched._released <= pos < sched._released + len(sched._window)) or j >= self.batch_num:
+            return None
+        if (self.batch_index + j) % self.batch_num not in sched._window:
+            return None
+        return self._get_arr(int(j))
 
     def get_cur_shape(self):
         return tuple([len(self.sched.get_input_index_array(self.batch_index))] + list(self.raw_data.shape[1:]))

@@ -899,8 +899,9 @@ int ha_cache_lookup_presorted(ha_cache *cache, const void *keys, int key_kind, i
  * batch; the first call allocates the ring (not inside a stream capture).  Results: those of ha_cache_lookup. */
 int ha_cache_sort_ahead_batch(ha_cache *cache, const void *const *keys, int key_kind, const int64_t *n, int count,
                               ha_stream_t stream);
-/* The PLANNED flow (csrc/cache_block.hip; LRU, local store, limit >= max_batch): CacheBase::_embeddingLookup and
- * _embeddingUpdate of the same keys, batch after batch (src/hetu_cache/src/cache.cc:60-107, 132-197; the training loop of
+/* The PLANNED flow (csrc/cache_block.hip; LRU, LFU, LFUOpt over a local store -- device or pinned host memory --, LRU with
+ * limit >= max_batch): CacheBase::_embeddingLookup and _embeddingUpdate (ha_cache_plan_block) or _embeddingUpdateWithPushKeys
+ * (ha_cache_plan_block_push_keys) of the same keys, batch after batch (src/hetu_cache/src/cache.cc:60-107, 132-197; the training loop of
  * python/hetu/cstable.py:38-56), with the BOOKKEEPING of a block of up to 16 batches done ahead: which lines a batch hits and
  * misses, the slots of the misses, the lines the policy evicts for them (LRUCache::insert lru_cache.cc:9-25; LFUCache
  * lfu_cache.cc:9-42 and LFUOptCache lfuopt_cache.cc:9-60: the least (use, arrival) of all lines, kept as a two-level minimum
@@ -917,6 +918,24 @@ int ha_cache_sort_ahead_batch(ha_cache *cache, const void *const *keys, int key_
  * ha_cache_snapshot see the bookkeeping of every planned batch, i.e. are meaningful at the end of a block. */
 int ha_cache_plan_block(ha_cache *cache, const void *const *keys, int key_kind, const int64_t *n, int count,
                         ha_stream_t side, ha_stream_t main);
+/* ha_cache_plan_block for batches whose update is CacheBase::_embeddingUpdateWithPushKeys (cache.cc:248-335; the laia
+ * scheduler's push plans): a line is pushed iff its key is one of the batch's push keys and the line holds data; push_bound
+ * plays no part; EVERY line of the batch gets version += its update counter, pushed or not, and only pushed lines start their
+ * gradient and counter again at 0; pending evictions are pushed as usual.  LFU / LFUOpt: a key whose insert did not stay, or
+ * whose line the batch's own first insert evicted, reaches the update as a line without data -- not pushed, its gradient
+ * dropped (the evicted line itself is pushed as an eviction).  Per batch i: push_keys[i] = n_push[i] keys of `push_kind`
+ * (0 float32, 1 64-bit integers, independent of key_kind), SORTED ascending (duplicates allowed), 0 <= n_push[i] <= max_batch
+ * (0: only evictions are pushed); n_push[i] < 0 plans batch i in bound mode (as ha_cache_plan_block), so one block may mix both.
+ * The push-key buffers follow the keys' rule: unchanged until the bookkeeping has run.  The lookups and updates are
+ * ha_cache_lookup_planned / ha_cache_update_planned / ha_cache_run_planned_pairs, unchanged.  Results: those of
+ * ha_cache_lookup + ha_cache_update_with_push_keys call by call.
+ * Ordering: this entry point ALWAYS orders its work on `side` behind everything enqueued on `main` so far (ids and push keys
+ * written there just before the call are read as written).  ha_cache_plan_block does so only for the first blocks and after
+ * call-by-call calls; in steady state it waits only for the rows of the block that last used its buffers, so key buffers it is
+ * given must be complete by other means. */
+int ha_cache_plan_block_push_keys(ha_cache *cache, const void *const *keys, int key_kind, const int64_t *n,
+                                  const void *const *push_keys, int push_kind, const int64_t *n_push, int count,
+                                  ha_stream_t side, ha_stream_t main);
 int ha_cache_lookup_planned(ha_cache *cache, int64_t n, float *dest, ha_stream_t stream);
 int ha_cache_update_planned(ha_cache *cache, int64_t n, const float *grads, ha_stream_t stream);
 int ha_cache_plan_pending(ha_cache *cache);
