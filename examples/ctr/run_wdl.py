@@ -18,7 +18,9 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
   --embedding ps     row-range sharded store (one shard per rank): SparsePull / SparsePush through
                      ParameterServerCommunicateOp                     (comm_mode PS; torchrun for N > 1)
   --embedding cache  HET cache (LRU / LFU / LFUOpt, bounded staleness) in front of the store
-                     (comm_mode Hybrid + --cache POLICY --bound B, run_hetu.py:178-190)
+                     (comm_mode Hybrid + --cache POLICY --bound B, run_hetu.py:178-190).  With --cache-planned on one rank
+                     the cache's bookkeeping runs a batch ahead: at --bsp 0 as planned lookup + update pairs, at the
+                     default --bsp -1 (asp, --cache lru) as the planned push-pull chain, one cache call per step.
 
   --laia             the reference's run_laia.py loop (examples/ctr/run_laia.py:214-236): every rank runs the laia
                      scheduler over the whole sample set (herald_amd.laia.LAIAScheduler: LaiaScheduler, or with
@@ -220,8 +222,12 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
-    --embedding cache at bsp 0 on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
-    batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  a2a / allreduce: optional
+    --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
+    batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
+    planned lookup + update pairs; at bsp < 0 (asp, the command line's default) with the LRU policy the planned push-pull chain:
+    one cache call per training step, which needs cache_limit >= 2 * batch * 26 (the default limit takes that into account).
+    The ring wraps round, so the chain is still open when training ends, with one step's bookkeeping planned ahead and never
+    run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
     replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests)."""
     dev = torch.device(device)
     import torch.distributed as dist
@@ -252,7 +258,8 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
         param = hetu_ops.EmbeddingParameter(store=store)
         config = hetu_ops.Config(comm_mode="PS" if embedding == "ps" else "Hybrid", bsp=bsp, prefetch=True,
                                  cstable_policy=cache if embedding == "cache" else None, cache_bound=bound,
-                                 cache_limit=cache_limit if cache_limit is not None else max(rows // 10, batch * NFIELD),
+                                 cache_limit=cache_limit if cache_limit is not None else
+                                 max(rows // 10, batch * NFIELD * (2 if cache_planned and bsp < 0 else 1)),
                                  cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned)
         comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: ids_of(state["k"] + 1),
                                                      peek_ids=lambda j: ids_of(state["k"] + 1 + j))
@@ -379,8 +386,10 @@ def main():
     ap.add_argument("--cache", default=None, help="cache policy: lru | lfu | lfuopt (with --comm PS / Hybrid)")
     ap.add_argument("--bound", type=int, default=100, help="cache bound")
     ap.add_argument("--cache-planned", action="store_true",
-                    help="--embedding cache at --bsp 0, or --laia: the cache's planned flow (bookkeeping of the next batch beside "
-                         "this step; --laia: the update pushes the batch's push plan).  With --laia at world size > 1 it is "
+                    help="--embedding cache, or --laia: the cache's planned flow (bookkeeping of the next batch beside "
+                         "this step; --bsp 0: planned lookup + update pairs; --bsp -1, the default, with --cache lru: the planned "
+                         "push-pull chain, one cache call per step, cache limit >= 2 * batch * 26; "
+                         "--laia: the update pushes the batch's push plan).  With --laia at world size > 1 it is "
                          "accepted and has no effect (the cache there talks to a remote store, call by call)")
     ap.add_argument("--nepoch", type=int, default=-1, help="epochs of `--steps` steps each (default: one)")
     ap.add_argument("--embedding", choices=["hbm", "step", "step3", "queue", "ps", "cache"], default=None,

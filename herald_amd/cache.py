@@ -421,7 +421,7 @@ class _CacheBase:
                   "ha_cache_sort_ahead_batch")
 
     # ---- the planned flow: the bookkeeping of a block of batches ahead, ONE launch per lookup / update ----------------------
-    def plan_block(self, keys_list, side=None, push_keys_list=None):
+    def plan_block(self, keys_list, side=None, push_keys_list=None, push_pull=False):
         """State that the device tensors of `keys_list` (1..16, one dtype, at most min(max_batch, 36,864) keys each) are the
         batches of the NEXT embedding_lookup_planned / embedding_update_planned pairs, in this order (ha_cache_plan_block,
         csrc/cache_block.hip: a local store; LRU: limit >= the batch; LFU / LFUOpt: every resident line updated since its lookup, as
@@ -435,9 +435,28 @@ class _CacheBase:
         push_keys_list (optional, one entry per batch): the batch's update is embedding_update_with_push_keys (cache.cc:248-335)
         with these push keys -- a sorted device tensor, float32 or (u)int64, at most max_batch keys, unchanged until the
         bookkeeping has run (ha_cache_plan_block_push_keys) -- or, for a None entry, the bounded push of embedding_update.  The
-        planned lookups and updates are the same calls either way."""
+        planned lookups and updates are the same calls either way.
+
+        push_pull=True (LRU only): the entries are the next steps of a PUSH-PULL CHAIN (ha_cache_plan_block_push_pull, cache.cc:356-422,
+        the asp-with-prefetch schedule): entry i's step pulls batch i and pushes the batch of the entry before it, across blocks.
+        The chain's first step has nothing to push and is made by embedding_lookup_planned; a None entry, allowed as the last
+        one, closes the chain: its step is embedding_update_planned with the gradients of the batch pulled last; every other
+        step is embedding_push_pull_planned(dest, grads).  Every step needs n_pull + n_push <= limit.  While a chain is open the
+        call-by-call methods and pair blocks raise; push_keys_list must be None."""
         if self._remote is not None or not keys_list:
             raise ValueError("plan_block: a non-empty list of key tensors, local store")
+        closes = False
+        if push_pull:
+            if push_keys_list is not None:
+                raise ValueError("plan_block: push keys are not part of a push-pull chain (push_keys_list must be None)")
+            if any(k is None for k in keys_list[:-1]):
+                raise ValueError("plan_block: only the last entry of a push-pull block may be None (it closes the chain)")
+            closes = keys_list[-1] is None
+            if closes and len(keys_list) == 1 and getattr(self, "_chain_last", None) is None:
+                raise ValueError("plan_block: no push-pull chain is open (nothing to close)")
+            if len(keys_list) > 16:
+                raise ValueError("plan_block: 1-16 key tensors of one dtype")
+            keys_list = list(keys_list[:-1]) if closes else list(keys_list)
         pks = None
         if push_keys_list is not None:
             # (everything is checked before anything is enqueued)
@@ -490,6 +509,30 @@ class _CacheBase:
             side = self._plan_side
         ks = [self._keys(k, []) for k in keys_list]
         kinds = {kind for _, kind in ks}
+        if push_pull:
+            if len(kinds) > 1 or any(not k.is_cuda for k, _ in ks):
+                raise ValueError("plan_block: 1-16 device key tensors of one dtype")
+            last = getattr(self, "_chain_last", None)
+            kind = kinds.pop() if kinds else (0 if last.dtype == torch.float32 else 1)
+            cnt = len(ks) + (1 if closes else 0)
+            ptrs = (ctypes.c_void_p * cnt)(*([k.data_ptr() if k.numel() else None for k, _ in ks] + ([None] if closes else [])))
+            ns = (ctypes.c_int64 * cnt)(*([k.numel() for k, _ in ks] + ([-1] if closes else [])))
+            self._ahead = None
+            self._drop_ahead_ring()
+            self._last_lookup = None
+            check(self._L.ha_cache_plan_block_push_pull(self._h, ptrs, kind, ns, cnt, ctypes.c_void_p(side.cuda_stream),
+                                                        ctypes.c_void_p(s.cuda_stream)), "ha_cache_plan_block_push_pull")
+            if not hasattr(self, "_chain"):
+                self._chain = []
+            # [kind, pull key tensor, push key tensor]: both kept alive until the step is made (a batch is used by two steps)
+            for k, _ in ks:
+                self._chain.append(["head" if last is None else "step", k, last])
+                last = k
+            if closes:
+                self._chain.append(["close", None, last])
+                last = None
+            self._chain_last = last
+            return
         if len(kinds) != 1 or len(ks) > 16:
             raise ValueError("plan_block: 1-16 key tensors of one dtype")
         ptrs = (ctypes.c_void_p * len(ks))(*[k.data_ptr() if k.numel() else None for k, _ in ks])
@@ -520,31 +563,91 @@ class _CacheBase:
 
     def embedding_lookup_planned(self, dest):
         """The lookup of the next planned batch (cache.cc:60-107), ONE launch; dest: float32 device tensor [n, width]."""
-        if not getattr(self, "_planned", None) or self._planned[0][1]:
+        chain = getattr(self, "_chain", None)
+        if chain:
+            if chain[0][0] != "head":
+                raise ValueError("embedding_lookup_planned: the step of the push-pull chain that is due is not its head")
+            k = chain[0][1]
+        elif not getattr(self, "_planned", None) or self._planned[0][1]:
             raise ValueError("embedding_lookup_planned: no planned batch is due for its lookup")
-        k = self._planned[0][0]
+        else:
+            k = self._planned[0][0]
         s = self._stream()
         assert dest.is_cuda and dest.dtype == torch.float32 and dest.numel() == k.numel() * self._width
         check(self._L.ha_cache_lookup_planned(self._h, k.numel(), ctypes.c_void_p(dest.data_ptr() if k.numel() else None),
                                               ctypes.c_void_p(s.cuda_stream)), "ha_cache_lookup_planned")
-        self._planned[0][1] = True
+        if chain:
+            chain.pop(0)
+        else:
+            self._planned[0][1] = True
         if self.perf_enabled:
             self._perf_record(0)
         return Wait(s, [k, dest]) if self._planned_waits else None
 
     def embedding_update_planned(self, grads):
         """The update of the planned batch whose lookup was the last planned call (cache.cc:132-197), ONE launch."""
-        if not getattr(self, "_planned", None) or not self._planned[0][1]:
+        chain = getattr(self, "_chain", None)
+        if chain:
+            if chain[0][0] != "close":
+                raise ValueError("embedding_update_planned: the step of the push-pull chain that is due is not its closing one")
+            k = chain[0][2]
+        elif not getattr(self, "_planned", None) or not self._planned[0][1]:
             raise ValueError("embedding_update_planned: the lookup of the planned batch comes first")
-        k = self._planned[0][0]
+        else:
+            k = self._planned[0][0]
         s = self._stream()
         assert grads.is_cuda and grads.dtype == torch.float32 and grads.is_contiguous() and grads.numel() == k.numel() * self._width
         check(self._L.ha_cache_update_planned(self._h, k.numel(), ctypes.c_void_p(grads.data_ptr() if k.numel() else None),
                                               ctypes.c_void_p(s.cuda_stream)), "ha_cache_update_planned")
-        self._planned.pop(0)
+        if chain:
+            chain.pop(0)
+        else:
+            self._planned.pop(0)
         if self.perf_enabled:
             self._perf_record(1)
         return Wait(s, [k, grads]) if self._planned_waits else None
+
+    def _chain_step_args(self, who, j, dest, grads):
+        chain = getattr(self, "_chain", None) or []
+        if j >= len(chain) or chain[j][0] != "step":
+            raise ValueError("%s: no push-pull step is due (the chain's head is embedding_lookup_planned, its closing step "
+                             "embedding_update_planned)" % who)
+        pull, push = chain[j][1], chain[j][2]
+        if not (torch.is_tensor(dest) and dest.is_cuda and dest.dtype == torch.float32 and dest.is_contiguous() and
+                dest.numel() == pull.numel() * self._width):
+            raise ValueError("%s: dest must be a contiguous float32 device tensor [%d, %d]" % (who, pull.numel(), self._width))
+        if not (torch.is_tensor(grads) and grads.is_cuda and grads.dtype == torch.float32 and grads.is_contiguous() and
+                grads.numel() == push.numel() * self._width):
+            raise ValueError("%s: grads must be a contiguous float32 device tensor [%d, %d]" % (who, push.numel(), self._width))
+        return pull, push
+
+    def embedding_push_pull_planned(self, dest, grads):
+        """The next step of the planned push-pull chain (cache.cc:356-422): the gradients `grads` of the batch pulled by the step
+        before are accumulated and pushed, then the step's own batch is pulled into dest.  ONE library call, two launches, no
+        bookkeeping on the cache's stream; no perf record (the reference's _embeddingPushPull appends none)."""
+        pull, push = self._chain_step_args("embedding_push_pull_planned", 0, dest, grads)
+        s = self._stream()
+        check(self._L.ha_cache_push_pull_planned(self._h, pull.numel(), ctypes.c_void_p(dest.data_ptr() if pull.numel() else None),
+                                                 push.numel(), ctypes.c_void_p(grads.data_ptr() if push.numel() else None),
+                                                 ctypes.c_void_p(s.cuda_stream)), "ha_cache_push_pull_planned")
+        self._chain.pop(0)
+        return Wait(s, [pull, push, dest, grads]) if self._planned_waits else None
+
+    def run_planned_push_pulls(self, dests, grads):
+        """The next len(dests) steps of the chain by ONE library call (ha_cache_run_planned_push_pulls): step k pulls into
+        dests[k] and pushes grads[k].  For callers that have the gradient buffers at hand (a benchmark loop)."""
+        cnt = len(dests)
+        if len(grads) != cnt:
+            raise ValueError("run_planned_push_pulls: %d dests, %d grads" % (cnt, len(grads)))
+        kk = [self._chain_step_args("run_planned_push_pulls", j, dests[j], grads[j]) for j in range(cnt)]
+        s = self._stream()
+        npl = (ctypes.c_int64 * cnt)(*[a.numel() for a, _ in kk])
+        nps = (ctypes.c_int64 * cnt)(*[b.numel() for _, b in kk])
+        dp = (ctypes.c_void_p * cnt)(*[d.data_ptr() if d.numel() else None for d in dests])
+        gp = (ctypes.c_void_p * cnt)(*[g.data_ptr() if g.numel() else None for g in grads])
+        check(self._L.ha_cache_run_planned_push_pulls(self._h, cnt, npl, dp, nps, gp, ctypes.c_void_p(s.cuda_stream)),
+              "ha_cache_run_planned_push_pulls")
+        del self._chain[:cnt]
 
     def run_planned_pairs(self, dests, grads):
         """The next len(dests) planned pairs by ONE library call (ha_cache_run_planned_pairs): lookup into dests[k], update with
@@ -860,8 +963,15 @@ class CacheSparseTable:
 
     # the planned flow (csrc/cache_block.hip): the ids of a block of batches a block early -- bookkeeping ahead on a side stream,
     # ONE launch per lookup and per update
-    def plan_block(self, keys_list, side=None, push_keys_list=None):
-        self.cache.plan_block([k[0] if isinstance(k, tuple) else k for k in keys_list], side, push_keys_list)
+    def plan_block(self, keys_list, side=None, push_keys_list=None, push_pull=False):
+        self.cache.plan_block([k[0] if isinstance(k, tuple) else k for k in keys_list], side, push_keys_list, push_pull)
+
+    def embedding_push_pull_planned(self, dest, grads, sync=False):
+        w = self.cache.embedding_push_pull_planned(dest, grads)
+        return self._finish(w, sync) if w is not None else None
+
+    def run_planned_push_pulls(self, dests, grads):
+        self.cache.run_planned_push_pulls(dests, grads)
 
     def embedding_lookup_planned(self, dest, sync=False):
         w = self.cache.embedding_lookup_planned(dest)

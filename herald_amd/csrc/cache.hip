@@ -1860,6 +1860,7 @@ extern "C" int ha_cache_set_bounds(ha_cache *h, int64_t pull_bound, int64_t push
 extern "C" int ha_cache_set_bypass(ha_cache *h, int bypass) {
     HA_REQUIRE(h, "cache: null handle");
     HA_REQUIRE(ha_cache_plan_pending(h) == 0, "cache_set_bypass: planned batches are outstanding");
+    HA_CACHE_CHAIN_CLOSED(h, "cache_set_bypass");
     h->c.bypass = bypass != 0;
     return 0;
 }
@@ -2077,6 +2078,8 @@ extern "C" int ha_cache_outbox_pad(ha_cache *h, int64_t entries) {
 extern "C" int ha_cache_sort_ahead(ha_cache *h, const void *keys, int key_kind, int64_t n, ha_stream_t stream) {
     HA_REQUIRE(h && (key_kind == 0 || key_kind == 1) && n >= 0 && (n == 0 || keys), "cache_sort_ahead: bad arguments");
     HA_REQUIRE(n <= h->c.nmax, "cache: batch of %ld keys exceeds max_batch %ld", (long)n, (long)h->c.nmax);
+    if (n > 0)
+        HA_CACHE_CHAIN_CLOSED(h, "cache_sort_ahead");
     hipStream_t s = as_stream(stream);
     if (!h->ahead_stream) {
         HA_REQUIRE(hipStreamCreateWithFlags(&h->ahead_stream, hipStreamNonBlocking) == hipSuccess &&
@@ -2117,6 +2120,7 @@ extern "C" int ha_cache_sort_ahead_batch(ha_cache *h, const void *const *keys, i
     h->ring_head = 0;
     if (count == 0)
         return 0;
+    HA_CACHE_CHAIN_CLOSED(h, "cache_sort_ahead_batch");
     for (int i = 0; i < count; ++i) {
         HA_REQUIRE(n[i] > 0 && n[i] <= kSmallMax && n[i] <= h->c.nmax && keys[i] != nullptr,
                    "cache_sort_ahead_batch: batch %d of %ld keys (1 .. min(max_batch, %d) per batch)", i, (long)n[i], kSmallMax);
@@ -2180,6 +2184,7 @@ static int cache_lookup_impl(ha_cache *h, const void *keys, int key_kind, int64_
     HA_REQUIRE(n >= 0 && (n == 0 || (keys && dest)), "cache_lookup: bad arguments");
     HA_REQUIRE(ha_cache_plan_pending(h) == 0, "cache: %d planned calls are outstanding (ha_cache_plan_block): ha_cache_lookup_planned / "
                "ha_cache_update_planned come first", ha_cache_plan_pending(h));
+    HA_CACHE_CHAIN_CLOSED(h, "cache_lookup");
     h->last_planned_type = -1;
     h->lfu_tree_ok = false;
     Cache &c = h->c;
@@ -2247,6 +2252,7 @@ static int cache_update_impl(ha_cache *h, const void *keys, int key_kind, int64_
     HA_REQUIRE(n >= 0 && (n == 0 || grads), "cache_update: bad arguments");
     HA_REQUIRE(ha_cache_plan_pending(h) == 0, "cache: %d planned calls are outstanding (ha_cache_plan_block): ha_cache_lookup_planned / "
                "ha_cache_update_planned come first", ha_cache_plan_pending(h));
+    HA_CACHE_CHAIN_CLOSED(h, "cache_update");
     h->last_planned_type = -1;
     h->lfu_tree_ok = false;
     Cache &c = h->c;
@@ -2372,6 +2378,7 @@ static int push_pull_begin(ha_cache *h, const void *pull_keys, int pull_kind, in
                "cache_push_pull: null pointer");
     HA_REQUIRE(ha_cache_plan_pending(h) == 0, "cache: %d planned calls are outstanding (ha_cache_plan_block): ha_cache_lookup_planned / "
                "ha_cache_update_planned come first", ha_cache_plan_pending(h));
+    HA_CACHE_CHAIN_CLOSED(h, "cache_push_pull");
     h->last_planned_type = -1;
     h->lfu_tree_ok = false;
     Cache &c = h->c;
@@ -2581,6 +2588,8 @@ extern "C" int ha_cache_snapshot(ha_cache *h, int64_t cap, uint32_t *keys, int64
     for (PlanSlot &sl : h->plan)
         if (sl.booked && sl.count > 0)
             HA_CHECK_HIP(hipStreamWaitEvent(as_stream(stream), sl.booked, 0));
+    if (cache_chain_settle(h, as_stream(stream)))       // (an open push-pull chain: versions staged by its last pull half)
+        return -1;
     hipLaunchKernelGGL(cache_snapshot_kernel, dim3(1024), dim3(256), 0, as_stream(stream), h->c,
                        (long long)cap, keys, reinterpret_cast<long long *>(version), updates,
                        reinterpret_cast<unsigned long long *>(stamp), slots,

@@ -28,6 +28,12 @@
 //                           line's new gradient (store row += grad, grad = 0), a wave per evicted dirty line (store row += its
 //                           gradient), a thread per line for versions.
 //
+//   ha_cache_plan_block_push_pull / ha_cache_push_pull_planned
+//                           the same idea for _embeddingPushPull (cache.cc:356-422), the asp-with-prefetch schedule's one call
+//                           per step (LRU): a CHAIN of steps, each pulling a batch and pushing the batch pulled by the step before
+//                           -- cache_book_chain_kernel on the side stream, then per step the update launch (push half) and the
+//                           lookup launch (pull half, which takes the push half's version commit back for its decision).
+//
 // Field ownership while a block is planned: the bookkeeping launch owns slot_of, a line's key / state / stamp / updates, the
 // stamp log, the free stack and the control block (all accessed device-coherently inside the launch: `sc1` loads / stores,
 // MI355X_MICROARCH.md "inter-workgroup visibility"); the row launches own data, grad, hasgrad, a line's version, the store's
@@ -144,6 +150,150 @@ __device__ __forceinline__ uint32_t book_rank(bool f, uint32_t *s_w4, uint32_t *
     return off + below;
 }
 
+// The stamp log is nearly full: compact it (valid entries keep their order), a tile of kBookWg x 256 entries at a time.
+// Returns false when an exchange gave up.
+__device__ __forceinline__ bool book_compact_log(const Cache &c, CacheCtl *ctl, unsigned long long *xw, unsigned long long &seq,
+                                                 long long head, long long &tail, uint32_t *s_a, uint32_t *s_b, uint32_t *s_w4,
+                                                 int *s_abort) {
+    const int tid = threadIdx.x, g = blockIdx.x;
+    long long wr = head;
+    for (long long t0 = head; t0 < tail; t0 += kBookWg * kBookThreads) {
+        const long long e = t0 + g * kBookThreads + tid;
+        int ls = -1;
+        unsigned long long lst = 0;
+        bool valid = false;
+        if (e < tail) {
+            ls = static_cast<int>(ldc(c.log_slot + e % c.Lcap));
+            lst = ldc(c.log_stamp + e % c.Lcap);
+            const unsigned long long st = ldc(line_word(c.line, ls, 0));
+            const unsigned long long w3 = ldc(line_word(c.line, ls, 3));
+            valid = static_cast<uint8_t>(w3 >> 32) == kResident && st == lst;
+        }
+        uint32_t tot;
+        const uint32_t r = book_rank(valid, s_w4, &tot);
+        if (!book_exchange(ctl, xw, ++seq, tot, 0, s_a, s_b, s_abort))
+            return false;
+        uint32_t before = 0, all = 0;
+        for (int k = 0; k < kBookWg; ++k) {
+            before += k < g ? s_a[k] : 0u;
+            all += s_a[k];
+        }
+        if (valid) {      // (positions below this tile's first entry: read by everybody before the exchange)
+            stc(c.log_slot + (wr + before + r) % c.Lcap, static_cast<uint32_t>(ls));
+            stc(c.log_stamp + (wr + before + r) % c.Lcap, lst);
+        }
+        wr += all;
+    }
+    tail = wr;
+    if (!book_exchange(ctl, xw, ++seq, 0, 0, s_a, s_b, s_abort))
+        return false;
+    return true;
+}
+
+// LRUCache::insert's evictions (lru_cache.cc:9-25): the first `need` VALID entries from the log's head (valid: the line is
+// resident and still carries the entry's stamp; entries at `tail` and beyond are not looked at).  Their slots go back on the
+// free stack above the M entries the batch's misses took; the dirty ones (updates != 0) are listed in ev_*.
+struct BookEvicted {
+    long long new_head, evicted;
+    uint32_t dirty;
+};
+__device__ __forceinline__ bool book_evict(const Cache &c, CacheCtl *ctl, unsigned long long *xw, unsigned long long &seq,
+                                           long long need, long long head, long long tail, long long ftop, uint32_t M,
+                                           int32_t *ev_slot, uint32_t *ev_key, int32_t *ev_upd, BookEvicted *out, uint32_t *s_a,
+                                           uint32_t *s_b, uint32_t *s_w4, int *s_abort,
+                                           uint32_t step = 0) {
+    const int tid = threadIdx.x, g = blockIdx.x;
+    const long long need0 = need;
+    uint32_t taken_before = 0, dirty_before = 0;      // victims / dirty victims of the rounds before this one
+    long long new_head = head;
+    while (need > 0 && new_head < tail) {
+        const long long e = new_head + g * kBookThreads + tid;
+        int ls = -1;
+        unsigned long long lst = 0, w2 = 0;
+        bool valid = false;
+        if (e < tail) {
+            ls = static_cast<int>(ldc(c.log_slot + e % c.Lcap));
+            lst = ldc(c.log_stamp + e % c.Lcap);
+            const unsigned long long st = ldc(line_word(c.line, ls, 0));
+            w2 = ldc(line_word(c.line, ls, 2));
+            const unsigned long long w3 = ldc(line_word(c.line, ls, 3));
+            valid = static_cast<uint8_t>(w3 >> 32) == kResident && st == lst;
+            // (a push-pull chain: never a line that step `step` or the one before pulled, see cache_book_chain_kernel's marks)
+            if (step != 0u && (static_cast<uint32_t>(w3) == step || static_cast<uint32_t>(w3) == step - 1u))
+                valid = false;
+        }
+        const bool dirty = valid && static_cast<uint32_t>(w2 >> 32) != 0u;
+        uint32_t tv, td;
+        const uint32_t rv = book_rank(valid, s_w4, &tv);
+        const uint32_t rd = book_rank(dirty, s_w4, &td);
+        if (!book_exchange(ctl, xw, ++seq, tv, td, s_a, s_b, s_abort))
+            return false;
+        uint32_t vb = 0, db = 0, vall = 0;
+        for (int k = 0; k < kBookWg; ++k) {
+            vb += k < g ? s_a[k] : 0u;
+            db += k < g ? s_b[k] : 0u;
+            vall += s_a[k];
+        }
+        const bool take = valid && static_cast<long long>(vb + rv) < need;
+        if (take) {
+            const uint32_t key = static_cast<uint32_t>(w2);
+            stc(c.slot_of + key, -1);
+            stc(line_word(c.line, ls, 3), line_w3(kFree, false));
+            stc(c.free_list + (ftop - M + taken_before + vb + rv), ls);
+            if (dirty) {      // every valid entry in front of a victim is a victim: its rank among the dirty victims
+                const long long at_e = dirty_before + db + rd;
+                ev_slot[at_e] = ls;
+                ev_key[at_e] = key;
+                ev_upd[at_e] = static_cast<int32_t>(w2 >> 32);
+            }
+        }
+        // the round's last victim tells everybody where the log's head is now, and how many dirty lines were taken
+        const bool last = take && static_cast<long long>(vb + rv) == need - 1;
+        const bool all_taken = static_cast<long long>(vall) <= need;
+        uint32_t adv = 0, dcut = 0;
+        if (last) {
+            adv = static_cast<uint32_t>(e + 1 - new_head);
+            dcut = db + rd + (dirty ? 1u : 0u);
+        }
+        if (!all_taken || static_cast<long long>(vall) == need) {
+            // the cut is inside this round: one thread holds it
+            const unsigned long long mm = __ballot(last);
+            __syncthreads();
+            if (tid < 2)
+                s_w4[tid] = 0;
+            __syncthreads();
+            if (mm != 0ull && lane_id() == __builtin_ctzll(mm)) {
+                s_w4[0] = adv;
+                s_w4[1] = dcut;
+            }
+            __syncthreads();
+            if (!book_exchange(ctl, xw, ++seq, s_w4[0], s_w4[1], s_a, s_b, s_abort))
+                return false;
+            uint32_t A = 0, D = 0;
+            for (int k = 0; k < kBookWg; ++k) {
+                A += s_a[k];
+                D += s_b[k];
+            }
+            new_head += A;
+            dirty_before += D;
+            taken_before += static_cast<uint32_t>(need);
+            need = 0;
+        } else {
+            uint32_t dall = 0;
+            for (int k = 0; k < kBookWg; ++k)
+                dall += s_b[k];
+            new_head = min(new_head + static_cast<long long>(kBookWg) * kBookThreads, tail);
+            taken_before += vall;
+            dirty_before += dall;
+            need -= vall;
+        }
+    }
+    out->new_head = new_head;
+    out->evicted = need0 - need;
+    out->dirty = dirty_before;
+    return true;
+}
+
 // ---- the bookkeeping of a block of batches ---------------------------------------------------------------------------------
 // Per batch i (its unique keys u = 0 .. U-1 in key order, as `Unique<T>` hands them to batchedLookup, cache.cc:15-26,66-68):
 //   every line of the batch ends the pair lookup + update as the cache's newest, in key order: stamp = clock + u, log entry
@@ -186,36 +336,7 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_block_kernel(Cache c,
         const uint8_t *pkm = a.pk_mark[i];      // (every line of the batch that the update finds holds data)
         // ---- log nearly full: compact it first (valid entries keep their order), a tile of kBookWg x 256 entries at a time
         if (tail - head > c.Lcap - 4 * c.nmax - 2048 - kBookWg * kBookThreads) {
-            long long wr = head;
-            for (long long t0 = head; t0 < tail; t0 += kBookWg * kBookThreads) {
-                const long long e = t0 + g * kBookThreads + tid;
-                int ls = -1;
-                unsigned long long lst = 0;
-                bool valid = false;
-                if (e < tail) {
-                    ls = static_cast<int>(ldc(c.log_slot + e % c.Lcap));
-                    lst = ldc(c.log_stamp + e % c.Lcap);
-                    const unsigned long long st = ldc(line_word(c.line, ls, 0));
-                    const unsigned long long w3 = ldc(line_word(c.line, ls, 3));
-                    valid = static_cast<uint8_t>(w3 >> 32) == kResident && st == lst;
-                }
-                uint32_t tot;
-                const uint32_t r = book_rank(valid, s_w4, &tot);
-                if (!book_exchange(ctl, a.xw, ++seq, tot, 0, s_a, s_b, &s_abort))
-                    return;
-                uint32_t before = 0, all = 0;
-                for (int k = 0; k < kBookWg; ++k) {
-                    before += k < g ? s_a[k] : 0u;
-                    all += s_a[k];
-                }
-                if (valid) {      // (positions below this tile's first entry: read by everybody before the exchange)
-                    stc(c.log_slot + (wr + before + r) % c.Lcap, static_cast<uint32_t>(ls));
-                    stc(c.log_stamp + (wr + before + r) % c.Lcap, lst);
-                }
-                wr += all;
-            }
-            tail = wr;
-            if (!book_exchange(ctl, a.xw, ++seq, 0, 0, s_a, s_b, &s_abort))
+            if (!book_compact_log(c, ctl, a.xw, seq, head, tail, s_a, s_b, s_w4, &s_abort))
                 return;
         }
         // ---- phase 1: probe; hits are touched and counted at once -----------------------------------------------------------
@@ -297,90 +418,12 @@ __global__ __launch_bounds__(kBookThreads) void cache_book_block_kernel(Cache c,
             }
         }
         // ---- phase 3: LRUCache::insert's evictions --------------------------------------------------------------------------
-        long long need = size + M > c.limit ? size + M - c.limit : 0;
-        const long long need0 = need;
-        uint32_t taken_before = 0, dirty_before = 0;      // victims / dirty victims of the rounds before this one
-        long long new_head = head;
-        while (need > 0 && new_head < tail) {
-            const long long e = new_head + g * kBookThreads + tid;
-            int ls = -1;
-            unsigned long long lst = 0, w2 = 0;
-            bool valid = false;
-            if (e < tail) {
-                ls = static_cast<int>(ldc(c.log_slot + e % c.Lcap));
-                lst = ldc(c.log_stamp + e % c.Lcap);
-                const unsigned long long st = ldc(line_word(c.line, ls, 0));
-                w2 = ldc(line_word(c.line, ls, 2));
-                const unsigned long long w3 = ldc(line_word(c.line, ls, 3));
-                valid = static_cast<uint8_t>(w3 >> 32) == kResident && st == lst;
-            }
-            const bool dirty = valid && static_cast<uint32_t>(w2 >> 32) != 0u;
-            uint32_t tv, td;
-            const uint32_t rv = book_rank(valid, s_w4, &tv);
-            const uint32_t rd = book_rank(dirty, s_w4, &td);
-            if (!book_exchange(ctl, a.xw, ++seq, tv, td, s_a, s_b, &s_abort))
-                return;
-            uint32_t vb = 0, db = 0, vall = 0;
-            for (int k = 0; k < kBookWg; ++k) {
-                vb += k < g ? s_a[k] : 0u;
-                db += k < g ? s_b[k] : 0u;
-                vall += s_a[k];
-            }
-            const bool take = valid && static_cast<long long>(vb + rv) < need;
-            if (take) {
-                const uint32_t key = static_cast<uint32_t>(w2);
-                stc(c.slot_of + key, -1);
-                stc(line_word(c.line, ls, 3), line_w3(kFree, false));
-                stc(c.free_list + (ftop - M + taken_before + vb + rv), ls);
-                if (dirty) {      // every valid entry in front of a victim is a victim: its rank among the dirty victims
-                    const long long at_e = at + dirty_before + db + rd;
-                    a.ev_slot[at_e] = ls;
-                    a.ev_key[at_e] = key;
-                    a.ev_upd[at_e] = static_cast<int32_t>(w2 >> 32);
-                }
-            }
-            // the round's last victim tells everybody where the log's head is now, and how many dirty lines were taken
-            const bool last = take && static_cast<long long>(vb + rv) == need - 1;
-            const bool all_taken = static_cast<long long>(vall) <= need;
-            uint32_t adv = 0, dcut = 0;
-            if (last) {
-                adv = static_cast<uint32_t>(e + 1 - new_head);
-                dcut = db + rd + (dirty ? 1u : 0u);
-            }
-            if (!all_taken || static_cast<long long>(vall) == need) {
-                // the cut is inside this round: one thread holds it
-                const unsigned long long mm = __ballot(last);
-                __syncthreads();
-                if (tid < 2)
-                    s_w4[tid] = 0;
-                __syncthreads();
-                if (mm != 0ull && lane_id() == __builtin_ctzll(mm)) {
-                    s_w4[0] = adv;
-                    s_w4[1] = dcut;
-                }
-                __syncthreads();
-                if (!book_exchange(ctl, a.xw, ++seq, s_w4[0], s_w4[1], s_a, s_b, &s_abort))
-                    return;
-                uint32_t A = 0, D = 0;
-                for (int k = 0; k < kBookWg; ++k) {
-                    A += s_a[k];
-                    D += s_b[k];
-                }
-                new_head += A;
-                dirty_before += D;
-                taken_before += static_cast<uint32_t>(need);
-                need = 0;
-            } else {
-                uint32_t dall = 0;
-                for (int k = 0; k < kBookWg; ++k)
-                    dall += s_b[k];
-                new_head = min(new_head + static_cast<long long>(kBookWg) * kBookThreads, tail);
-                taken_before += vall;
-                dirty_before += dall;
-                need -= vall;
-            }
-        }
-        const long long evicted = need0 - need;
+        BookEvicted ev;
+        if (!book_evict(c, ctl, a.xw, seq, size + M > c.limit ? size + M - c.limit : 0, head, tail, ftop, M, a.ev_slot + at,
+                        a.ev_key + at, a.ev_upd + at, &ev, s_a, s_b, s_w4, &s_abort))
+            return;
+        const long long new_head = ev.new_head, evicted = ev.evicted;
+        const uint32_t dirty_before = ev.dirty;
         // ---- the batch is booked -------------------------------------------------------------------------------------------
         head = new_head;
         ftop = ftop - M + evicted;
@@ -945,10 +988,14 @@ __global__ __launch_bounds__(256) void cache_plan_expand_kernel(BookArgs a, Plan
 // different rows per lane, 256-thread workgroups -- 11.3 us against 9.1 for a wave per position; without the two version reads
 // 9.07 against 9.29 us; without the row stores 7.65: the launch is the part's "copy of 6,656 random 2 KB rows" (DESIGN.md
 // section 6, yardstick: 8.0 us), the staleness check is almost free beside it.)
-template <int VEC>
+// PP (the pull half of a push-pull step, launched BEHIND the step's push half): vadj[p] = the update counter that the push half
+// has just added to the line's version because it pushed the line (0: it did not).  cache.cc judges staleness with the version
+// as it is BEFORE that commit (:404 against :414-421) and adds the counter AFTER the pull, so the commit is taken back for the
+// decision and a pulled line's staged version is the store's version + the counter.
+template <int VEC, bool PP = false>
 __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
     Cache c, const int4 *__restrict__ pos_item, long long n, float *__restrict__ dest, long long *__restrict__ pver,
-    const PlanRec *__restrict__ rec) {
+    const PlanRec *__restrict__ rec, const int32_t *__restrict__ vadj = nullptr) {
     const int lane = lane_id();
     const long long p = static_cast<long long>(blockIdx.x) * 16ll + uniform(static_cast<int>(threadIdx.x >> 6));
     if (p >= n)
@@ -987,7 +1034,12 @@ __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
     float *line = c.data + static_cast<long long>(s) * c.width;
     const bool is_miss = (fl & kPosMiss) != 0;
     const long long sv = c.srv_ver[lk];
-    const long long v = is_miss ? -1 : c.line[s].version;
+    long long v = is_miss ? -1 : c.line[s].version;
+    long long adj = 0;
+    if (PP) {
+        adj = static_cast<long long>(uniform(vadj[p]));
+        v = v == -1 ? -1 : v - adj;
+    }
     // the cached row, requested beside the two versions (a hit that is not stale -- the usual case -- has it on the way)
     float4v x0{0.f, 0.f, 0.f, 0.f}, x1 = x0;
     const long long j0 = lane * 4, j1 = j0 + kWave * 4;
@@ -1039,7 +1091,7 @@ __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
         }
     }
     if (head && lane == 0)
-        pver[p] = sv;
+        pver[p] = sv + adj;
 }
 
 // ---- the update of a planned batch: ONE launch -----------------------------------------------------------------------------
@@ -1137,6 +1189,305 @@ __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
     }
 }
 
+// ---- the bookkeeping of a block of a PUSH-PULL CHAIN (LRU) -------------------------------------------------------------------
+// Step i of the block is CacheBase::_embeddingPushPull (cache.cc:356-422) with pull = batch i (unique keys u = 0 .. Up-1) and
+// push = the batch of the step before (v = 0 .. Uq-1, every occurrence counted in counts_q); the chain's head has no push side
+// (_embeddingLookup, :60-107), its closing step no pull side (_embeddingUpdate, :132-197).  In the reference's order:
+//   the pull batch's hits are touched in key order, then EVERY push key (a key of both batches ends at its push touch), then the
+//   pull misses are inserted in key order as the newest lines, each taking a slot from the free stack; LRUCache::insert evicts
+//   from the old end.  The host has checked n_pull + n_push <= limit: no line the step touches is among its victims, and every
+//   push key -- pulled by the step before -- is still resident (a push key that is not: sticky word 4).
+//   Only the PUSH touch is stamped and logged (stamp clock + v): every line a step pulls is a push key of the NEXT step (the
+//   closing step included) and is touched there again, in key order as well, before any eviction could look at it -- its place
+//   among the lines that can be evicted is decided by push touches alone.  Until then the eviction walk passes over it by its
+//   mark (ChainArgs), and a new line carries a stamp of its own that no log entry has (clock + Uq + miss rank).
+//   A push line's counter grows by its occurrences; beyond push_bound it is pushed and starts again at 0 (:392,414-420).
+//   The dirty victims are NOT pushed by this step: they wait (evict_, :378) for the next one, whose push half reads this step's
+//   ev_* list.  ctl->evict_n carries their number from launch to launch; the closing step leaves 0.
+// What the row launches get: per unique pull key {slot, kPosMiss, kPosInit: the line has a gradient buffer when the pull half
+// runs (it had one, or the push half gives it one), the version adjust: its counter if this step pushes it, else 0 -- see
+// cache_lookup_planned_kernel<.., PP>}; per unique push key {slot, kPosInit, kPosPush, kItemKeep, the counter after the step}.
+// kItemKeep: a line pushed AND pulled by the step keeps its gradient row through the push (Line::addup of the pull still adds
+// it, :404 is in front of zeroGrad :419); its bookkeeping copy of hasgrad is cleared instead, so the next step's accumulate --
+// the line is a key of the batch pulled now, so it is pushed again by the next step -- starts from zero (no kPosInit).
+constexpr uint8_t kItemKeep = 1;      // (q_flag only: the bit kPosMiss has in a pull item)
+constexpr uint32_t kLogNoSlot = 0;
+constexpr unsigned long long kLogNoStamp = ~0ull;      // a log entry that is never valid (no line carries this stamp)
+struct ChainArgs {
+    int count;
+    int n_p[kPlanBlockMax];              // keys of the step's pull batch (-1: the closing step)
+    int n_q[kPlanBlockMax];              // keys of its push batch (0: the chain's head, or an empty batch)
+    const PlanHeader *hdr_p[kPlanBlockMax], *hdr_q[kPlanBlockMax];
+    const uint32_t *uniq_p[kPlanBlockMax], *uniq_q[kPlanBlockMax];
+    const int32_t *counts_q[kPlanBlockMax];
+    int32_t *it_slot;        // [count][nmax] pull side, per unique key
+    uint8_t *it_flag;
+    int32_t *it_upd;         // the version adjust
+    int32_t *q_slot;         // [count][nmax] push side, per unique key of the batch before
+    uint8_t *q_flag;
+    int32_t *q_upd;
+    int32_t *ev_slot;        // [count][nmax] the dirty lines this step's insert evicted (pushed by the NEXT step)
+    uint32_t *ev_key;
+    int32_t *ev_upd;
+    PlanRec *rec;
+    unsigned long long *xw;
+    long long nmax;
+    // "is this line a key of the step's OTHER batch, and which": every line that step number t pulls (hit or miss, unique key
+    // u) carries the MARK (t, u) in its record's word 3 (chain_w3: the LRU policy has no use for `freq`).  Step t's pull side
+    // finds the marks of step t - 1 (whose pull batch is its push batch), its push side the marks the pull side has just
+    // written, the eviction walk both -- in the record it reads anyway, instead of a binary search per key
+    unsigned long long step0;            // number of the block's first step (32 bits are kept; numbers start at 2)
+};
+// a line record's word 3 with a mark: step | state << 32 | hg << 40 | u << 48
+__device__ __forceinline__ unsigned long long chain_w3(unsigned long long step, uint8_t state, bool hg, uint32_t u) {
+    return (step & 0xFFFFFFFFull) | line_w3(state, hg) | (static_cast<unsigned long long>(u) << 48);
+}
+static_assert(kSmallMax <= 65536, "a mark keeps the position among a batch's unique keys in 16 bits");
+__global__ __launch_bounds__(kBookThreads) void cache_book_chain_kernel(Cache c, ChainArgs a) {
+    __shared__ uint32_t s_a[kBookWg], s_b[kBookWg], s_w4[kBookThreads / 64];
+    __shared__ int s_abort;
+    CacheCtl *ctl = c.ctl;
+    const int tid = threadIdx.x, g = blockIdx.x;
+    if (tid == 0)
+        s_abort = 0;
+    long long clock = ctl->clock, tail = ctl->log_tail, head = ctl->log_head, ftop = ctl->free_top, size = ctl->size;
+    long long pend = ctl->evict_n;      // dirty lines the step before evicted: this step's push half pushes them
+    unsigned long long seq = static_cast<unsigned long long>(ctl->book_seq);
+    __syncthreads();
+    for (int i = 0; i < a.count; ++i) {
+        const int np = a.n_p[i], nq = a.n_q[i];
+        const long long at = static_cast<long long>(i) * a.nmax;
+        const unsigned long long t = a.step0 + static_cast<unsigned long long>(i);
+        const uint32_t t32 = static_cast<uint32_t>(t), tb32 = static_cast<uint32_t>(t - 1ull);
+        const int Up = np > 0 ? static_cast<int>(a.hdr_p[i]->n_unique) : 0;
+        const int Uq = nq > 0 ? static_cast<int>(a.hdr_q[i]->n_unique) : 0;
+        const uint32_t *uniq_p = a.uniq_p[i], *uniq_q = a.uniq_q[i];
+        const int32_t *counts_q = a.counts_q[i];
+        if (tail - head > c.Lcap - 4 * c.nmax - 2048 - kBookWg * kBookThreads) {
+            if (!book_compact_log(c, ctl, a.xw, seq, head, tail, s_a, s_b, s_w4, &s_abort))
+                return;
+        }
+        // ---- everything the step READS of the lines, requested together: both batches' slots, then their line words -----------
+        // (nothing is written before these loads are back except words nobody reads here; the push side's STORES wait behind
+        // the exchange: the pull side of another workgroup reads the counter and the hasgrad copy of a line of both batches)
+        const int per = (Up + kBookWg - 1) / kBookWg;
+        const int u0 = min(g * per, Up), u1 = min(u0 + per, Up);
+        const int perq = (Uq + kBookWg - 1) / kBookWg;
+        const int v0 = min(g * perq, Uq), v1 = min(v0 + perq, Uq);
+        uint32_t kk[kBookKeysPerThread], rk[kBookKeysPerThread], kq[kBookKeysPerThread];
+        int sp[kBookKeysPerThread], sq[kBookKeysPerThread];
+        bool miss[kBookKeysPerThread];
+        unsigned long long pw2[kBookKeysPerThread], pw3[kBookKeysPerThread], qw2[kBookKeysPerThread];
+        uint32_t wg_miss = 0;
+#pragma unroll
+        for (int j = 0; j < kBookKeysPerThread; ++j) {
+            const int u = u0 + j * kBookThreads + tid, v = v0 + j * kBookThreads + tid;
+            kk[j] = u < u1 ? uniq_p[u] : 0xFFFFFFFFu;
+            kq[j] = v < v1 ? uniq_q[v] : 0xFFFFFFFFu;
+            sp[j] = u < u1 && kk[j] < static_cast<unsigned long long>(c.length) ? ldc(c.slot_of + kk[j]) : -1;
+            sq[j] = v < v1 && kq[j] < static_cast<unsigned long long>(c.length) ? ldc(c.slot_of + kq[j]) : -1;
+            miss[j] = u < u1 && kk[j] < static_cast<unsigned long long>(c.length) && sp[j] < 0;
+        }
+#pragma unroll
+        for (int j = 0; j < kBookKeysPerThread; ++j) {
+            pw2[j] = pw3[j] = qw2[j] = 0ull;
+            if (sp[j] >= 0) {
+                pw2[j] = ldc(line_word(c.line, sp[j], 2));
+                pw3[j] = ldc(line_word(c.line, sp[j], 3));
+            }
+            if (sq[j] >= 0)
+                qw2[j] = ldc(line_word(c.line, sq[j], 2));
+        }
+        // ---- the pull side: marks, items, the misses' ranks (no stamp: see the header) ----------------------------------------
+#pragma unroll
+        for (int j = 0; j < kBookKeysPerThread; ++j) {
+            const int u = u0 + j * kBookThreads + tid;
+            if (u < u1) {
+                const int s = sp[j];
+                int vq = s >= 0 && Uq > 0 && static_cast<uint32_t>(pw3[j]) == tb32 ? static_cast<int>(pw3[j] >> 48) : -1;
+                vq = vq < Uq ? vq : -1;      // (a mark of the step before names a key of its batch: always below Uq)
+                if (s >= 0) {
+                    stc(line_word(c.line, s, 3), chain_w3(t, kResident, ((pw3[j] >> 40) & 1ull) != 0ull, static_cast<uint32_t>(u)));
+                    int adj = 0;
+                    if (vq >= 0) {
+                        const int upd = static_cast<int>(pw2[j] >> 32) + counts_q[vq];
+                        adj = upd > c.push_bound ? upd : 0;
+                    }
+                    a.it_slot[at + u] = s;
+                    a.it_flag[at + u] = static_cast<uint8_t>((((pw3[j] >> 40) & 1ull) != 0ull || vq >= 0) ? kPosInit : 0);
+                    a.it_upd[at + u] = adj;
+                } else if (!miss[j]) {
+                    a.it_slot[at + u] = -1;
+                    a.it_flag[at + u] = 0;
+                    a.it_upd[at + u] = 0;
+                }
+            }
+            uint32_t tot;
+            rk[j] = wg_miss + book_rank(miss[j], s_w4, &tot);
+            wg_miss += tot;
+        }
+        if (!book_exchange(ctl, a.xw, ++seq, wg_miss, 0, s_a, s_b, &s_abort))
+            return;
+        uint32_t mb = 0, M = 0;
+        for (int k = 0; k < kBookWg; ++k) {
+            mb += k < g ? s_a[k] : 0u;
+            M += s_a[k];
+        }
+        // ---- the push side: every key is touched; counters, the bounded push -------------------------------------------------
+#pragma unroll
+        for (int j = 0; j < kBookKeysPerThread; ++j) {
+            const int v = v0 + j * kBookThreads + tid;
+            if (v >= v1)
+                continue;
+            const uint32_t key = kq[j];
+            const int s = sq[j];
+            const long long pos = (tail + v) % c.Lcap;
+            if (s < 0) {      // beyond the cache's range: ignored; in range: cannot be (see the header)
+                if (key < static_cast<unsigned long long>(c.length))
+                    ctl->fb_timeout = 4;
+                stc(c.log_slot + pos, kLogNoSlot);
+                stc(c.log_stamp + pos, kLogNoStamp);
+                a.q_slot[at + v] = -1;
+                a.q_flag[at + v] = 0;
+                a.q_upd[at + v] = 0;
+                continue;
+            }
+            const unsigned long long w3 = ldc(line_word(c.line, s, 3));      // (with the mark of this step's pull side, if any)
+            const bool hg = ((w3 >> 40) & 1ull) != 0ull;
+            const int upd = static_cast<int>(qw2[j] >> 32) + counts_q[v];
+            const bool push = upd > c.push_bound;
+            const bool keep = push && static_cast<uint32_t>(w3) == t32;
+            const unsigned long long st = static_cast<unsigned long long>(clock + v);
+            stc(line_word(c.line, s, 0), st);
+            stc(line_word(c.line, s, 2), static_cast<unsigned long long>(key) |
+                                             (static_cast<unsigned long long>(static_cast<uint32_t>(push ? 0 : upd)) << 32));
+            if (hg == keep)      // the accumulate gives the line its gradient buffer; a kept one counts as none afterwards
+                stc(line_word(c.line, s, 3), (w3 & ~(0xFFull << 40)) | (keep ? 0ull : 1ull << 40));
+            stc(c.log_slot + pos, static_cast<uint32_t>(s));
+            stc(c.log_stamp + pos, st);
+            a.q_slot[at + v] = s;
+            a.q_flag[at + v] = static_cast<uint8_t>((hg ? kPosInit : 0) | (push ? kPosPush : 0) | (keep ? kItemKeep : 0));
+            a.q_upd[at + v] = upd;
+        }
+        // ---- the pull misses become lines, the newest of all -----------------------------------------------------------------
+#pragma unroll
+        for (int j = 0; j < kBookKeysPerThread; ++j) {
+            const int u = u0 + j * kBookThreads + tid;
+            if (u < u1 && miss[j]) {
+                const long long r = static_cast<long long>(mb + rk[j]);
+                const long long fi = ftop - 1 - r;
+                const int s = fi >= 0 ? ldc(c.free_list + fi) : 0;     // (running out of slots: sizing, checked on the host)
+                // (a stamp no log entry carries: the slot's last line left its own behind)
+                stc(line_word(c.line, s, 0), static_cast<unsigned long long>(clock + Uq + r));
+                stc(line_word(c.line, s, 2), static_cast<unsigned long long>(kk[j]));
+                stc(line_word(c.line, s, 3), chain_w3(t, kResident, false, static_cast<uint32_t>(u)));
+                stc(c.slot_of + kk[j], s);
+                a.it_slot[at + u] = s;
+                a.it_flag[at + u] = static_cast<uint8_t>(kPosMiss);
+                a.it_upd[at + u] = 0;
+            }
+        }
+        // ---- LRUCache::insert's evictions: never a line this step or the step before pulled (by their marks: the first carry
+        //      the stamps of their last push touch, the second are re-stamped by other workgroups just now) --------------------
+        BookEvicted ev;
+        if (!book_evict(c, ctl, a.xw, seq, size + M > c.limit ? size + M - c.limit : 0, head, tail, ftop, M, a.ev_slot + at,
+                        a.ev_key + at, a.ev_upd + at, &ev, s_a, s_b, s_w4, &s_abort, t32))
+            return;
+        head = ev.new_head;
+        ftop = ftop - M + ev.evicted;
+        size = size + M - ev.evicted;
+        tail += Uq;
+        clock += static_cast<long long>(Uq) + M;
+        if (g == 0 && tid == 0) {
+            PlanRec r{};
+            r.n = np >= 0 ? np : nq;      // (the closing step reports as the update it is: the perf dict's Push record)
+            r.U = np >= 0 ? Up : Uq;
+            r.M = M;
+            r.E = ev.dirty;
+            r.evicted = ev.evicted;
+            r.size = size;
+            r.full = size == c.limit;
+            r.npush = -1;
+            r.erep = np >= 0 ? static_cast<long long>(ev.dirty) : pend;
+            r.vh_slot = -1;
+            a.rec[i] = r;
+        }
+        pend = ev.dirty;
+        if (!book_exchange(ctl, a.xw, ++seq, 0, 0, s_a, s_b, &s_abort))
+            return;
+    }
+    if (g == 0 && tid == 0) {
+        ctl->clock = clock;
+        ctl->log_tail = tail;
+        ctl->log_head = head;
+        ctl->free_top = ftop;
+        ctl->size = size;
+        ctl->evict_n = pend;
+        ctl->book_seq = static_cast<long long>(seq);
+        ctl->U = 0;
+        ctl->M = 0;
+    }
+}
+
+// the items of a chain block per sorted position (as cache_plan_expand_kernel): blockIdx.z = 0 the pull side of entry
+// blockIdx.y (positions of its own batch), 1 the push side (positions of the batch before)
+struct ChainExpandPtrs {
+    int n[2][kPlanBlockMax];
+    const uint32_t *uniq[2][kPlanBlockMax];
+    const int32_t *upos[2][kPlanBlockMax];
+    const int32_t *perm[2][kPlanBlockMax];
+};
+__global__ __launch_bounds__(256) void cache_chain_expand_kernel(ChainArgs a, ChainExpandPtrs e, int4 *pos_item, int32_t *it_upd_pos,
+                                                                 int4 *q_pos_item, int32_t *q_upd_pos) {
+    const int i = blockIdx.y, side = blockIdx.z;
+    const int n = e.n[side][i];
+    const long long at = static_cast<long long>(i) * a.nmax;
+    const int32_t *upos = e.upos[side][i], *perm = e.perm[side][i];
+    const uint32_t *uniq = e.uniq[side][i];
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+        const int u = upos[p];
+        const int head = (p == 0 || upos[p - 1] != u) ? kPosHead : 0;
+        if (side == 0) {
+            pos_item[at + p] = int4{a.it_slot[at + u], static_cast<int>(uniq[u]), static_cast<int>(a.it_flag[at + u]) | head, perm[p]};
+            it_upd_pos[at + p] = a.it_upd[at + u];
+        } else {
+            const int f = a.q_flag[at + u];
+            q_pos_item[at + p] = int4{a.q_slot[at + u], static_cast<int>(uniq[u]),
+                                      (f & (kPosInit | kPosPush)) | ((f & kItemKeep) ? kPosKeep : 0) | head, perm[p]};
+            q_upd_pos[at + p] = a.q_upd[at + u];
+        }
+    }
+}
+
+// An open chain, looked at from outside (ha_cache_snapshot) while the last row call made is a pull half: the versions it staged
+// are committed (the next push half would do it: it finds kVerKeep then and keeps the line's version), and the gradient rows
+// that the step's push half kept for it (kPosKeep) are zeroed -- what Line::zeroGrad leaves (nothing reads them again: the
+// next accumulate of such a line carries no kPosInit).  A wave per sorted position.
+__global__ __launch_bounds__(1024) void cache_chain_settle_kernel(Cache c, const int4 *__restrict__ pos_item, long long n,
+                                                                  long long *__restrict__ pver, const int4 *__restrict__ q_pos_item,
+                                                                  long long nq) {
+    const int lane = lane_id();
+    const long long p = static_cast<long long>(blockIdx.x) * 16ll + uniform(static_cast<int>(threadIdx.x >> 6));
+    if (p < n) {
+        const int4 it = pos_item[p];
+        if (lane == 0 && it.x >= 0 && it.x < c.S && (it.z & kPosHead)) {
+            const long long pv = pver[p];
+            if (pv != kVerKeep) {
+                c.line[it.x].version = pv;
+                pver[p] = kVerKeep;
+            }
+        }
+    }
+    if (p < nq) {
+        const int4 it = q_pos_item[p];
+        if (it.x >= 0 && it.x < c.S && (it.z & kPosHead) && (it.z & kPosKeep)) {
+            float *g = c.grad + static_cast<long long>(it.x) * c.width;
+            for (long long j = lane; j < c.width; j += kWave)
+                g[j] = 0.f;
+        }
+    }
+}
+
 // the perf dict's data-dependent counts of a planned batch, on demand: lines the lookup pulled, lines the update pushed
 __global__ __launch_bounds__(1024) void cache_plan_count_kernel(PlanRec *rec, const long long *pver, const int4 *pos_item) {
     __shared__ unsigned long long s_p[16], s_q[16];
@@ -1219,7 +1570,7 @@ extern "C" int ha_cache_plan_pending(ha_cache *h) {
         return 0;
     int pending = 0;
     for (const PlanSlot &sl : h->plan)
-        pending += sl.count > 0 ? 2 * sl.count - sl.next_call : 0;
+        pending += sl.count > 0 ? sl.total() - sl.next_call : 0;
     return pending;
 }
 
@@ -1247,6 +1598,7 @@ static int plan_block_impl(ha_cache *h, const void *const *keys, int key_kind, c
     HA_REQUIRE(c.row_start == 0 && c.store_rows >= c.length, "cache_plan_block: the store must hold every key of the cache's range");
 
     HA_REQUIRE(c.limit >= 1, "cache_plan_block: an empty cache");
+    HA_CACHE_CHAIN_CLOSED(h, "cache_plan_block");
     HA_REQUIRE(h->evict_empty || ha_cache_plan_pending(h) > 0, "cache_plan_block: evicted lines are pending (an update must follow "
                "the last lookup first)");
     HA_REQUIRE(h->ahead_n < 0, "cache_plan_block: a ha_cache_sort_ahead is pending");
@@ -1259,8 +1611,8 @@ static int plan_block_impl(ha_cache *h, const void *const *keys, int key_kind, c
     PlanSlot &sl = h->plan[h->plan_next % ha_cache::kPlanSlots];
     int blocks_out = 0;
     for (const PlanSlot &q : h->plan)
-        blocks_out += q.count > 0 && q.next_call < 2 * q.count ? 1 : 0;
-    HA_REQUIRE(blocks_out < 2 && (sl.count == 0 || sl.next_call >= 2 * sl.count),
+        blocks_out += q.count > 0 && q.next_call < q.total() ? 1 : 0;
+    HA_REQUIRE(blocks_out < 2 && (sl.count == 0 || sl.next_call >= sl.total()),
                "cache_plan_block: two planned blocks are outstanding already");
     if (plan_slot_alloc(h, sl))
         return -1;
@@ -1395,6 +1747,7 @@ static int plan_block_impl(ha_cache *h, const void *const *keys, int key_kind, c
     sl.count = count;
     sl.next_call = 0;
     sl.waited = false;
+    sl.pp = false;
     h->plan_next += 1;
     h->plan_n = -1;
     h->same_fast = false;
@@ -1414,12 +1767,179 @@ extern "C" int ha_cache_plan_block_push_keys(ha_cache *h, const void *const *key
     return plan_block_impl(h, keys, key_kind, n, push_keys, push_kind, n_push, count, side, main);
 }
 
-// the slot and batch index of the next planned call of `type` (0 lookup, 1 update)
+static int plan_slot_alloc_chain(ha_cache *h, PlanSlot &sl) {
+    if (sl.q_slot)
+        return 0;
+    const size_t all = static_cast<size_t>(h->c.nmax) * kPlanBlockMax;
+    HA_REQUIRE(dmalloc(&sl.q_slot, all) == 0 && dmalloc(&sl.q_flag, all) == 0 && dmalloc(&sl.q_upd, all) == 0 &&
+               dmalloc(&sl.q_pos_item, all) == 0 && dmalloc(&sl.q_upd_pos, all) == 0, "cache_plan_block_push_pull: out of device memory");
+    h->allocs.push_back(sl.q_slot);
+    h->allocs.push_back(sl.q_flag);
+    h->allocs.push_back(sl.q_upd);
+    h->allocs.push_back(sl.q_pos_item);
+    h->allocs.push_back(sl.q_upd_pos);
+    return 0;
+}
+
+// The bookkeeping of the next `count` (1..16) steps of a push-pull chain, see the header (include/herald_amd.h) and
+// cache_book_chain_kernel.  Everything is checked before anything is enqueued.
+extern "C" int ha_cache_plan_block_push_pull(ha_cache *h, const void *const *keys, int key_kind, const int64_t *n, int count,
+                                             ha_stream_t side, ha_stream_t main) {
+    HA_REQUIRE(h && keys && n && (key_kind == 0 || key_kind == 1) && count >= 1 && count <= kPlanBlockMax,
+               "cache_plan_block_push_pull: bad arguments (1..%d entries)", kPlanBlockMax);
+    Cache &c = h->c;
+    HA_REQUIRE(c.policy == kLRU, "cache_plan_block_push_pull: LRU only (the planned bookkeeping of LFU / LFUOpt rests on lookup + "
+               "update pairs of the same keys; those policies keep the call-by-call ha_cache_push_pull)");
+    HA_REQUIRE(c.table && !c.remote && !c.bypass, "cache_plan_block_push_pull: a cache over a local store, not bypassed");
+    HA_REQUIRE(c.row_start == 0 && c.store_rows >= c.length, "cache_plan_block_push_pull: the store must hold every key of the cache's range");
+    HA_REQUIRE(c.limit >= 1, "cache_plan_block_push_pull: an empty cache");
+    HA_REQUIRE(h->ahead_n < 0, "cache_plan_block_push_pull: a ha_cache_sort_ahead is pending");
+    HA_REQUIRE(h->chain_open || (ha_cache_plan_pending(h) == 0 && h->evict_empty),
+               "cache_plan_block_push_pull: a chain starts from a cache without planned calls outstanding and without pending evicted "
+               "lines (an update must follow the last lookup first)");
+    const bool closes = n[count - 1] < 0;
+    bool have_prev = h->chain_open;
+    int64_t prev_n = h->chain_n;
+    for (int i = 0; i < count; ++i) {
+        const bool close_i = n[i] < 0;
+        HA_REQUIRE(!close_i || i == count - 1, "cache_plan_block_push_pull: entry %d closes the chain, but only the last entry of a "
+                   "block may", i);
+        HA_REQUIRE(!close_i || have_prev, "cache_plan_block_push_pull: no chain is open (nothing to close)");
+        HA_REQUIRE(close_i || (n[i] <= c.nmax && n[i] <= kSmallMax && (n[i] == 0 || keys[i])),
+                   "cache_plan_block_push_pull: batch %d of %ld keys (at most min(max_batch, %d))", i, (long)n[i], kSmallMax);
+        const int64_t np = close_i ? 0 : n[i], nq = have_prev ? prev_n : 0;
+        HA_REQUIRE(np + nq <= c.limit, "cache_plan_block_push_pull: step %d pulls %ld and pushes %ld keys, limit is %ld: n_pull + "
+                   "n_push must not exceed limit (no line a step touches is evicted by the step's own insert)", i, (long)np, (long)nq,
+                   (long)c.limit);
+        have_prev = !close_i;
+        prev_n = np;
+    }
+    PlanSlot &sl = h->plan[h->plan_next % ha_cache::kPlanSlots];
+    int blocks_out = 0;
+    for (const PlanSlot &q : h->plan)
+        blocks_out += q.count > 0 && q.next_call < q.total() ? 1 : 0;
+    HA_REQUIRE(blocks_out < 2 && (sl.count == 0 || sl.next_call >= sl.total()),
+               "cache_plan_block_push_pull: two planned blocks are outstanding already");
+    if (plan_slot_alloc(h, sl) || plan_slot_alloc_chain(h, sl))
+        return -1;
+    if (!h->plan_xw) {
+        HA_REQUIRE(dmalloc(&h->plan_xw, static_cast<size_t>(4 * kBookWg)) == 0, "cache_plan_block_push_pull: out of device memory");
+        h->allocs.push_back(h->plan_xw);
+        if (dzero(h->plan_xw, 4 * kBookWg * 8))
+            return -1;
+        HA_CHECK_HIP(hipEventCreateWithFlags(&h->plan_fork, hipEventDisableTiming));
+    }
+    hipStream_t ss = as_stream(side), ms = as_stream(main);
+    if (ss != ms) {
+        // ids are often written on `main` just before this call: ALWAYS behind everything enqueued there so far
+        if (sl.rows_recorded)
+            HA_CHECK_HIP(hipStreamWaitEvent(ss, sl.rows_done, 0));
+        HA_CHECK_HIP(hipEventRecord(h->plan_fork, ms));
+        HA_CHECK_HIP(hipStreamWaitEvent(ss, h->plan_fork, 0));
+    }
+    PlanSlot &other = h->plan[(h->plan_next + ha_cache::kPlanSlots - 1) % ha_cache::kPlanSlots];
+    if (other.count > 0 && other.booked_on != ss)
+        HA_CHECK_HIP(hipStreamWaitEvent(ss, other.booked, 0));
+    const int built = count - (closes ? 1 : 0);
+    const uint64_t lim = static_cast<uint64_t>(c.length);
+    if (built > 0 &&
+        (key_kind == 0 ? ha_plan_build_batch_f32ids_lim(reinterpret_cast<const float *const *>(keys), n, sl.ws, built, lim, side)
+                       : ha_plan_build_batch_u64ids_lim(reinterpret_cast<const uint64_t *const *>(keys), n, sl.ws, built, lim, side)))
+        return -1;
+    ChainArgs a;
+    memset(&a, 0, sizeof(a));
+    ChainExpandPtrs ep;
+    memset(&ep, 0, sizeof(ep));
+    a.count = count;
+    have_prev = h->chain_open;
+    int nmx = 1;
+    for (int i = 0; i < count; ++i) {
+        const bool close_i = n[i] < 0;
+        const long long at = static_cast<long long>(i) * c.nmax;
+        sl.kind[i] = close_i ? kChainClose : have_prev ? kChainStep : kChainHead;
+        sl.n[i] = close_i ? -1 : n[i];
+        sl.pk[i] = false;
+        a.n_p[i] = close_i ? -1 : static_cast<int>(n[i]);
+        if (!close_i) {
+            PlanPtrs p = plan_layout(sl.ws[i], n[i]);
+            a.hdr_p[i] = p.hdr;
+            a.uniq_p[i] = p.uniq;
+            ep.n[0][i] = static_cast<int>(n[i]);
+            ep.uniq[0][i] = p.uniq;
+            ep.upos[0][i] = p.upos;
+            ep.perm[0][i] = p.perm;
+            nmx = n[i] > nmx ? static_cast<int>(n[i]) : nmx;
+        }
+        sl.q_n[i] = have_prev ? h->chain_n : 0;
+        if (have_prev) {
+            sl.q_ws[i] = h->chain_ws;
+            sl.q_pver[i] = h->chain_pver;
+            sl.q_ev_slot[i] = h->chain_ev_slot;
+            sl.q_ev_key[i] = h->chain_ev_key;
+            sl.q_ev_upd[i] = h->chain_ev_upd;
+            sl.q_rec[i] = h->chain_rec;
+            PlanPtrs q = plan_layout(h->chain_ws, h->chain_n);
+            a.n_q[i] = static_cast<int>(h->chain_n);
+            a.hdr_q[i] = q.hdr;
+            a.uniq_q[i] = q.uniq;
+            a.counts_q[i] = q.counts;
+            ep.n[1][i] = static_cast<int>(h->chain_n);
+            ep.uniq[1][i] = q.uniq;
+            ep.upos[1][i] = q.upos;
+            ep.perm[1][i] = q.perm;
+            nmx = h->chain_n > nmx ? static_cast<int>(h->chain_n) : nmx;
+        }
+        have_prev = !close_i;
+        if (have_prev) {
+            h->chain_n = n[i];
+            h->chain_ws = sl.ws[i];
+            h->chain_pver = sl.pver + at;
+            h->chain_ev_slot = sl.ev_slot + at;
+            h->chain_ev_key = sl.ev_key + at;
+            h->chain_ev_upd = sl.ev_upd + at;
+            h->chain_rec = sl.rec + i;
+        }
+    }
+    h->chain_open = have_prev;
+    a.it_slot = sl.it_slot; a.it_flag = sl.it_flag; a.it_upd = sl.it_upd;
+    a.q_slot = sl.q_slot; a.q_flag = sl.q_flag; a.q_upd = sl.q_upd;
+    a.ev_slot = sl.ev_slot; a.ev_key = sl.ev_key; a.ev_upd = sl.ev_upd;
+    a.rec = sl.rec;
+    a.xw = h->plan_xw;
+    a.nmax = c.nmax;
+    a.step0 = h->chain_step;
+    h->chain_step += static_cast<unsigned long long>(count);
+    hipLaunchKernelGGL(cache_book_chain_kernel, dim3(kBookWg), dim3(kBookThreads), 0, ss, c, a);
+    hipLaunchKernelGGL(cache_chain_expand_kernel, dim3((nmx + 255) / 256, count, 2), dim3(256), 0, ss, a, ep, sl.pos_item,
+                       sl.it_upd_pos, sl.q_pos_item, sl.q_upd_pos);
+    HA_LAUNCH_CHECK();
+    HA_CHECK_HIP(hipEventRecord(sl.booked, ss));
+    sl.booked_on = ss;
+    sl.count = count;
+    sl.next_call = 0;
+    sl.waited = false;
+    sl.pp = true;
+    h->plan_next += 1;
+    h->plan_n = -1;
+    h->same_fast = false;
+    h->ring_count = h->ring_head = 0;
+    h->evict_empty = false;       // (the chain's evicted lines wait for the next step; its closing update leaves none)
+    h->lfu_tree_ok = false;
+    return 0;
+}
+
+// the slot and entry index of the next planned call of `type` (0 lookup, 1 update, 2 push-pull); nullptr: another call is due
 static PlanSlot *plan_current(ha_cache *h, int type, int *idx) {
     for (int k = 0; k < ha_cache::kPlanSlots; ++k) {         // the older block first
         PlanSlot &sl = h->plan[(h->plan_next + k) % ha_cache::kPlanSlots];
-        if (sl.count > 0 && sl.next_call < 2 * sl.count) {
-            if ((sl.next_call & 1) != type)
+        if (sl.count > 0 && sl.next_call < sl.total()) {
+            if (sl.pp) {
+                if (sl.kind[sl.next_call] != (type == 0 ? kChainHead : type == 1 ? kChainClose : kChainStep))
+                    return nullptr;
+                *idx = sl.next_call;
+                return &sl;
+            }
+            if (type > 1 || (sl.next_call & 1) != type)
                 return nullptr;
             *idx = sl.next_call >> 1;
             return &sl;
@@ -1428,12 +1948,84 @@ static PlanSlot *plan_current(ha_cache *h, int type, int *idx) {
     return nullptr;
 }
 
+// the planned call (slot, entry, type) is enqueued
+static int plan_called(ha_cache *h, PlanSlot *sl, int i, int type, hipStream_t s) {
+    sl->next_call += 1;
+    if (sl->next_call == sl->total()) {       // the block's last row launch is enqueued
+        HA_CHECK_HIP(hipEventRecord(sl->rows_done, s));
+        sl->rows_recorded = true;
+    }
+    h->last_planned = sl;
+    h->last_planned_idx = i;
+    h->last_planned_type = type;
+    return 0;
+}
+
+// the row launch of a planned lookup / of a chain step's pull half (vadj != nullptr)
+static int lookup_rows(ha_cache *h, hipStream_t s, const int4 *pos_item, int64_t n, float *dest, long long *pver,
+                       const PlanRec *rec, const int32_t *vadj) {
+    Cache &c = h->c;
+    const unsigned blocks = static_cast<unsigned>((n + 15) / 16);
+    const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(dest) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
+    if (vadj == nullptr) {
+        if (vec_ok)
+            hipLaunchKernelGGL((cache_lookup_planned_kernel<4, false>), dim3(blocks), dim3(1024), 0, s, c, pos_item, (long long)n,
+                               dest, pver, rec, vadj);
+        else
+            hipLaunchKernelGGL((cache_lookup_planned_kernel<1, false>), dim3(blocks), dim3(1024), 0, s, c, pos_item, (long long)n,
+                               dest, pver, rec, vadj);
+    } else {
+        if (vec_ok)
+            hipLaunchKernelGGL((cache_lookup_planned_kernel<4, true>), dim3(blocks), dim3(1024), 0, s, c, pos_item, (long long)n,
+                               dest, pver, rec, vadj);
+        else
+            hipLaunchKernelGGL((cache_lookup_planned_kernel<1, true>), dim3(blocks), dim3(1024), 0, s, c, pos_item, (long long)n,
+                               dest, pver, rec, vadj);
+    }
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+// the row launch of a planned update / of a chain step's push half: the batch's index plan `ws`, its items per sorted position,
+// the versions its lookup staged, the evicted dirty lines to push with it (rec->E of them)
+static int update_rows(ha_cache *h, hipStream_t s, void *ws, int64_t n, const float *grads, const int4 *pos_item,
+                       const int32_t *it_upd_pos, const long long *pver, const int32_t *ev_slot, const uint32_t *ev_key,
+                       const int32_t *ev_upd, const PlanRec *rec, int pkmode) {
+    Cache &c = h->c;
+    PlanPtrs p = plan_layout(ws, n);
+    const int apply_blocks = static_cast<int>((n + kPosPerBlock - 1) / kPosPerBlock);
+    ApplyMaps maps{};
+    maps.dst2 = c.data;
+    maps.push_tab = c.table;
+    maps.push_rows = static_cast<uint64_t>(c.store_rows);
+    maps.pos_item = pos_item;
+    maps.victim_row = reinterpret_cast<const int *>(&rec->vh_slot);
+    const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(grads) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
+    const dim3 grid(static_cast<unsigned>(apply_blocks + kPlanEvictBlocks + kPlanMetaBlocks));
+    if (vec_ok)
+        hipLaunchKernelGGL(cache_update_planned_kernel<4>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
+                           grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+    else
+        hipLaunchKernelGGL(cache_update_planned_kernel<1>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
+                           grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+// ... of entry i of a chain block: the push half (the batch of the entry before)
+static int chain_push_rows(ha_cache *h, hipStream_t s, PlanSlot *sl, int i, const float *grads) {
+    const long long at = static_cast<long long>(i) * h->c.nmax;
+    return update_rows(h, s, sl->q_ws[i], sl->q_n[i], grads, sl->q_pos_item + at, sl->q_upd_pos + at, sl->q_pver[i],
+                       sl->q_ev_slot[i], sl->q_ev_key[i], sl->q_ev_upd[i], sl->q_rec[i], 0);
+}
+
 extern "C" int ha_cache_lookup_planned(ha_cache *h, int64_t n, float *dest, ha_stream_t stream) {
     HA_REQUIRE(h, "cache_lookup_planned: null handle");
     int i = 0;
     PlanSlot *sl = plan_current(h, 0, &i);
     HA_REQUIRE(sl != nullptr, "cache_lookup_planned: no planned batch is due for its lookup (ha_cache_plan_block; lookup and "
-               "update alternate)");
+               "update alternate; in a push-pull chain only the head is a lookup)");
     HA_REQUIRE(sl->n[i] == n && (n == 0 || dest), "cache_lookup_planned: the planned batch has %ld keys (got %ld)", (long)sl->n[i],
                (long)n);
     Cache &c = h->c;
@@ -1444,70 +2036,102 @@ extern "C" int ha_cache_lookup_planned(ha_cache *h, int64_t n, float *dest, ha_s
     }
     cache_mark(h, kTStart, s, true);
     if (n > 0) {
-        PlanPtrs p = plan_layout(sl->ws[i], n);
         const long long at = static_cast<long long>(i) * c.nmax;
-        const unsigned blocks = static_cast<unsigned>((n + 15) / 16);
-        const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(dest) % 16 == 0) &&
-                            (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
-        if (vec_ok)
-            hipLaunchKernelGGL(cache_lookup_planned_kernel<4>, dim3(blocks), dim3(1024), 0, s, c, sl->pos_item + at, (long long)n,
-                               dest, sl->pver + at, sl->rec + i);
-        else
-            hipLaunchKernelGGL(cache_lookup_planned_kernel<1>, dim3(blocks), dim3(1024), 0, s, c, sl->pos_item + at, (long long)n,
-                               dest, sl->pver + at, sl->rec + i);
-        HA_LAUNCH_CHECK();
+        if (lookup_rows(h, s, sl->pos_item + at, n, dest, sl->pver + at, sl->rec + i, nullptr))
+            return -1;
     }
     cache_mark(h, kTEnd, s);
-    sl->next_call += 1;
-    h->last_planned = sl;
-    h->last_planned_idx = i;
-    h->last_planned_type = 0;
-    return 0;
+    h->settle_slot = sl->pp ? sl : nullptr;
+    h->settle_idx = i;
+    return plan_called(h, sl, i, 0, s);
 }
 
 extern "C" int ha_cache_update_planned(ha_cache *h, int64_t n, const float *grads, ha_stream_t stream) {
     HA_REQUIRE(h, "cache_update_planned: null handle");
     int i = 0;
     PlanSlot *sl = plan_current(h, 1, &i);
-    HA_REQUIRE(sl != nullptr, "cache_update_planned: no planned batch is due for its update (its lookup comes first)");
-    HA_REQUIRE(sl->n[i] == n && (n == 0 || grads), "cache_update_planned: the planned batch has %ld keys (got %ld)", (long)sl->n[i],
+    HA_REQUIRE(sl != nullptr, "cache_update_planned: no planned batch is due for its update (its lookup comes first; in a push-pull "
+               "chain only the closing step is an update)");
+    const int64_t planned_n = sl->pp ? sl->q_n[i] : sl->n[i];
+    HA_REQUIRE(planned_n == n && (n == 0 || grads), "cache_update_planned: the planned batch has %ld keys (got %ld)", (long)planned_n,
                (long)n);
     Cache &c = h->c;
     hipStream_t s = as_stream(stream);
+    if (!sl->waited) {       // (a chain block whose only entry closes the chain)
+        HA_CHECK_HIP(hipStreamWaitEvent(s, sl->booked, 0));
+        sl->waited = true;
+    }
     cache_mark(h, kTStart, s, true);
     if (n > 0) {
-        PlanPtrs p = plan_layout(sl->ws[i], n);
         const long long at = static_cast<long long>(i) * c.nmax;
-        const int apply_blocks = static_cast<int>((n + kPosPerBlock - 1) / kPosPerBlock);
-        ApplyMaps maps{};
-        maps.dst2 = c.data;
-        maps.push_tab = c.table;
-        maps.push_rows = static_cast<uint64_t>(c.store_rows);
-        maps.pos_item = sl->pos_item + at;
-        maps.victim_row = reinterpret_cast<const int *>(&(sl->rec + i)->vh_slot);
-        const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(grads) % 16 == 0) &&
-                            (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
-        const dim3 grid(static_cast<unsigned>(apply_blocks + kPlanEvictBlocks + kPlanMetaBlocks));
-        if (vec_ok)
-            hipLaunchKernelGGL(cache_update_planned_kernel<4>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
-                               grads, maps, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at, sl->ev_key + at, sl->ev_upd + at,
-                               sl->rec + i, sl->pk[i] ? 1 : 0);
-        else
-            hipLaunchKernelGGL(cache_update_planned_kernel<1>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
-                               grads, maps, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at, sl->ev_key + at, sl->ev_upd + at,
-                               sl->rec + i, sl->pk[i] ? 1 : 0);
-        HA_LAUNCH_CHECK();
+        if (sl->pp ? chain_push_rows(h, s, sl, i, grads)
+                   : update_rows(h, s, sl->ws[i], n, grads, sl->pos_item + at, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at,
+                                 sl->ev_key + at, sl->ev_upd + at, sl->rec + i, sl->pk[i] ? 1 : 0))
+            return -1;
     }
     cache_mark(h, kTEnd, s);
-    sl->next_call += 1;
-    if (sl->next_call == 2 * sl->count) {       // the block's last row launch is enqueued
-        HA_CHECK_HIP(hipEventRecord(sl->rows_done, s));
-        sl->rows_recorded = true;
-    }
-    h->last_planned = sl;
-    h->last_planned_idx = i;
-    h->last_planned_type = 1;
+    h->settle_slot = nullptr;
     h->evict_empty = true;
+    return plan_called(h, sl, i, 1, s);
+}
+
+// A middle step of a push-pull chain (cache.cc:356-422): the push half of the batch pulled by the step before -- ordered
+// accumulate, the pushed lines' and the pending evicted lines' store side, versions -- then the pull half of the step's own
+// batch, whose staleness decision takes the push half's version commit back (cache_lookup_planned_kernel<.., PP>).  Two
+// launches on `stream`, no bookkeeping.
+extern "C" int ha_cache_push_pull_planned(ha_cache *h, int64_t n_pull, float *dest, int64_t n_push, const float *grads,
+                                          ha_stream_t stream) {
+    HA_REQUIRE(h, "cache_push_pull_planned: null handle");
+    int i = 0;
+    PlanSlot *sl = plan_current(h, 2, &i);
+    HA_REQUIRE(sl != nullptr, "cache_push_pull_planned: no push-pull step is due (ha_cache_plan_block_push_pull; the chain's head "
+               "is ha_cache_lookup_planned, its closing step ha_cache_update_planned)");
+    HA_REQUIRE(sl->n[i] == n_pull && sl->q_n[i] == n_push && (n_pull == 0 || dest) && (n_push == 0 || grads),
+               "cache_push_pull_planned: the planned step pulls %ld and pushes %ld keys (got %ld, %ld)", (long)sl->n[i],
+               (long)sl->q_n[i], (long)n_pull, (long)n_push);
+    Cache &c = h->c;
+    hipStream_t s = as_stream(stream);
+    if (!sl->waited) {
+        HA_CHECK_HIP(hipStreamWaitEvent(s, sl->booked, 0));
+        sl->waited = true;
+    }
+    const long long at = static_cast<long long>(i) * c.nmax;
+    cache_mark(h, kTStart, s, true);
+    if (n_push > 0 && chain_push_rows(h, s, sl, i, grads))
+        return -1;
+    cache_mark(h, kTCopy, s);
+    if (n_pull > 0 && lookup_rows(h, s, sl->pos_item + at, n_pull, dest, sl->pver + at, sl->rec + i, sl->it_upd_pos + at))
+        return -1;
+    cache_mark(h, kTEnd, s);
+    h->settle_slot = sl;
+    h->settle_idx = i;
+    return plan_called(h, sl, i, 2, s);
+}
+
+// `count` middle steps by ONE call (a caller that has the gradient buffers at hand: a benchmark loop)
+extern "C" int ha_cache_run_planned_push_pulls(ha_cache *h, int count, const int64_t *n_pull, float *const *dests,
+                                               const int64_t *n_push, const float *const *grads, ha_stream_t stream) {
+    HA_REQUIRE(h && count >= 0 && (count == 0 || (n_pull && dests && n_push && grads)), "cache_run_planned_push_pulls: bad arguments");
+    for (int k = 0; k < count; ++k)
+        if (ha_cache_push_pull_planned(h, n_pull[k], dests[k], n_push[k], grads[k], stream))
+            return -1;
+    return 0;
+}
+
+int ha::cache_chain_settle(ha_cache *h, hipStream_t s) {
+    PlanSlot *sl = h->settle_slot;
+    if (sl == nullptr)
+        return 0;
+    const int i = h->settle_idx;
+    const long long at = static_cast<long long>(i) * h->c.nmax;
+    const long long n = sl->n[i] > 0 ? sl->n[i] : 0, nq = sl->kind[i] == kChainStep ? sl->q_n[i] : 0;
+    const long long m = n > nq ? n : nq;
+    if (m > 0) {
+        hipLaunchKernelGGL(cache_chain_settle_kernel, dim3(static_cast<unsigned>((m + 15) / 16)), dim3(1024), 0, s, h->c,
+                           sl->pos_item + at, n, sl->pver + at, sl->q_pos_item + at, nq);
+        HA_LAUNCH_CHECK();
+    }
+    h->settle_slot = nullptr;
     return 0;
 }
 
@@ -1530,7 +2154,9 @@ int ha::cache_perf_planned(ha_cache *h, int64_t *out_host, hipStream_t s) {
     PlanSlot *sl = h->last_planned;
     const int i = h->last_planned_idx;
     const long long at = static_cast<long long>(i) * h->c.nmax;
-    hipLaunchKernelGGL(cache_plan_count_kernel, dim3(1), dim3(1024), 0, s, sl->rec + i, sl->pver + at, sl->pos_item + at);
+    // (the closing step of a push-pull chain: the pushed lines are flagged in the push side's items)
+    const int4 *items = (sl->pp && h->last_planned_type == 1 ? sl->q_pos_item : sl->pos_item) + at;
+    hipLaunchKernelGGL(cache_plan_count_kernel, dim3(1), dim3(1024), 0, s, sl->rec + i, sl->pver + at, items);
     PlanRec r;
     long long sticky = 0;
     HA_CHECK_HIP(hipMemcpyAsync(&r, sl->rec + i, sizeof(r), hipMemcpyDeviceToHost, s));

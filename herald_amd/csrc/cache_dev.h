@@ -150,12 +150,34 @@ struct PlanSlot {
     hipStream_t booked_on = nullptr;
     hipEvent_t rows_done = nullptr;     // behind the block's last row launch (recorded by its last ha_cache_update_planned)
     bool rows_recorded = false;
+    // ---- a block of a PUSH-PULL CHAIN (ha_cache_plan_block_push_pull): entry i is the step push_pull(pull = batch i, push = the
+    // batch of the entry before it); next_call = the entry that is due, `count` = consumed.  The pull side's items lie where a
+    // pair block keeps its items (it_upd: the version adjust, see cache_book_chain_kernel); the push side's -- per unique key /
+    // sorted position of the batch BEFORE -- in q_*.  What a step's push half reads of the entry before it (its index plan, its
+    // staged versions, the dirty lines its insert evicted) may lie in the slot of the block before: kept as pointers per entry.
+    bool pp = false;
+    int kind[kPlanBlockMax] = {};       // kChainHead: a plain lookup; kChainStep: push-pull; kChainClose: a plain update
+    int32_t *q_slot = nullptr;          // [kPlanBlockMax][nmax]
+    uint8_t *q_flag = nullptr;          // kPosInit | kPosPush | kItemKeep
+    int32_t *q_upd = nullptr;
+    int4 *q_pos_item = nullptr;
+    int32_t *q_upd_pos = nullptr;
+    int64_t q_n[kPlanBlockMax] = {};    // keys of the step's push batch
+    void *q_ws[kPlanBlockMax] = {};
+    long long *q_pver[kPlanBlockMax] = {};
+    int32_t *q_ev_slot[kPlanBlockMax] = {};
+    uint32_t *q_ev_key[kPlanBlockMax] = {};
+    int32_t *q_ev_upd[kPlanBlockMax] = {};
+    PlanRec *q_rec[kPlanBlockMax] = {};
+    int total() const { return pp ? count : 2 * count; }     // planned calls of the block
 };
+enum { kChainHead = 0, kChainStep = 1, kChainClose = 2 };
 }  // namespace ha
 
 struct ha_cache;
 namespace ha {
 int cache_perf_planned(ha_cache *h, int64_t *out_host, hipStream_t s);
+int cache_chain_settle(ha_cache *h, hipStream_t s);
 }
 
 struct ha_cache {
@@ -213,7 +235,26 @@ struct ha_cache {
     bool lfu_tree_ok = false;
     ha::PlanSlot *last_planned = nullptr;    // the last planned call: slot, batch, type (0 lookup / 1 update), for ha_cache_perf
     int last_planned_idx = 0, last_planned_type = -1;
+    // a push-pull chain: open = the last batch planned is pulled by its step and not yet pushed by a later one (set when a block
+    // is PLANNED); chain_* = what the next block's first step reads of that batch (see PlanSlot::q_*)
+    bool chain_open = false;
+    int64_t chain_n = 0;
+    void *chain_ws = nullptr;
+    long long *chain_pver = nullptr;
+    int32_t *chain_ev_slot = nullptr, *chain_ev_upd = nullptr;
+    uint32_t *chain_ev_key = nullptr;
+    ha::PlanRec *chain_rec = nullptr;
+    // number of the chain's next step (cache_book_chain_kernel marks the lines a step pulls with it; 0 and 1 are never given)
+    unsigned long long chain_step = 2;
+    // the last planned ROW call was the pull half of a chain step (or the chain's head): the versions it staged and the gradient
+    // rows it left for the next push half to overwrite are settled before anybody inspects the lines (cache_chain_settle)
+    ha::PlanSlot *settle_slot = nullptr;
+    int settle_idx = 0;
 };
+#define HA_CACHE_CHAIN_CLOSED(h, who)                                                                                          \
+    HA_REQUIRE(!(h)->chain_open, who ": a planned push-pull chain is open (a batch is pulled and not yet pushed): close it first " \
+               "-- plan a block whose only entry is the closing one (ha_cache_plan_block_push_pull, n = -1) and make its "          \
+               "ha_cache_update_planned call")
 
 enum { kTStart = 0, kTSort = 1, kTLookup = 2, kTCopy = 3, kTTransfer = 4, kTEnd = 5 };
 static inline void cache_mark(ha_cache *h, int slot, hipStream_t s, bool first = false) {

@@ -47,10 +47,12 @@ struct ApplyMaps {
     // kPosVictimPush is the key of the line the batch's own lookup evicted with updates pending (at most one per batch): its
     // push adds that line's old gradient row -- dst row *victim_row -- BEHIND its own (the evicted line follows the batch's
     // line of the same key in should_push, cache.cc:160-170).  kPosVictim / kPosVictimHg: for the lookup (cache_block.hip).
+    // kPosKeep (a planned push-pull step): the pushed line is pulled in the same step, and Line::addup of that pull still sees
+    // the gradient (cache.cc:404 runs in front of zeroGrad, :419) -- the first destination keeps its new value instead of zeros
     const int *victim_row;
 };
 enum : int { kPosMiss = 1, kPosInit = 2, kPosPush = 4, kPosHead = 8, kPosTemp = 16, kPosVictim = 32, kPosVictimHg = 64,
-             kPosVictimPush = 128 };
+             kPosVictimPush = 128, kPosKeep = 256 };
 
 // host: the run length from which the tolerance mode applies (0 = exact everywhere; scatter.hip,
 // ha_set_tolerance_mode)
@@ -66,6 +68,7 @@ struct Second {
     OptArgs oa;
     float *push;    // DUAL: the store row that takes the first destination's new value (nullptr: none), see ApplyMaps::push_tab
     const float *push2;   // DUAL == 2: a second row added to the store row behind it (nullptr: none), see ApplyMaps::victim_row
+    bool keep;            // DUAL == 2: the pushed first destination keeps its value (kPosKeep)
 };
 
 
@@ -207,7 +210,8 @@ struct Vec<1> {
 };
 
 template <int VEC>
-__device__ __forceinline__ void push_epilogue(float *__restrict__ push_row, int col, Vec<VEC> &acc, const float *push2 = nullptr) {
+__device__ __forceinline__ void push_epilogue(float *__restrict__ push_row, int col, Vec<VEC> &acc, const float *push2 = nullptr,
+                                              bool keep = false) {
     Vec<VEC> cur;
     cur.load(push_row + col);
 #pragma unroll
@@ -221,7 +225,8 @@ __device__ __forceinline__ void push_epilogue(float *__restrict__ push_row, int 
             cur.set(k, __fadd_rn(cur.get(k), old.get(k)));
     }
     cur.store(push_row + col);
-    acc.zero();
+    if (!keep)
+        acc.zero();
 }
 
 // ---- short runs (1..kShortRun occurrences): one wave, whole row --------------------------------
@@ -284,7 +289,7 @@ __device__ __forceinline__ void short_block(float *__restrict__ dst_row,
                     acc[b].set(k, __fadd_rn(cur[b].get(k), acc[b].get(k)));
             }
             if (DUAL == 2 && d2.push)
-                push_epilogue<VEC>(d2.push, col[b], acc[b], d2.push2);
+                push_epilogue<VEC>(d2.push, col[b], acc[b], d2.push2, d2.keep);
             if (MODE == kModeOpt) {
                 float gsum[VEC];
 #pragma unroll
@@ -406,7 +411,8 @@ __device__ __forceinline__ void medium_slice(float *__restrict__ dst_row,
             if (d2.push2)
                 pr = __fadd_rn(pr, d2.push2[col]);
             d2.push[col] = pr;
-            acc = 0.f;
+            if (!d2.keep)
+                acc = 0.f;
         }
         if (MODE == kModeOpt)
             opt_epilogue<1>(dst_row, d2, col, &acc);
@@ -781,7 +787,8 @@ __device__ __forceinline__ void coop_slices(
                 if (d2.push2)
                     pr = __fadd_rn(pr, d2.push2[ccol]);
                 d2.push[ccol] = pr;
-                acc = 0.f;
+                if (!d2.keep)
+                    acc = 0.f;
             }
             if (MODE == kModeOpt)
                 opt_epilogue<1>(dst_row, d2, ccol, &acc);
@@ -915,6 +922,7 @@ __device__ __forceinline__ bool coop_run(
                       ? maps.push_tab + static_cast<uint64_t>(static_cast<uint32_t>(pit.y)) * static_cast<uint64_t>(width)
                       : nullptr;
         d2.push2 = (pit.z & kPosVictimPush) ? dst + static_cast<uint64_t>(*maps.victim_row) * static_cast<uint64_t>(width) : nullptr;
+        d2.keep = (pit.z & kPosKeep) != 0;
     } else if (DUAL && maps.rowmap2) {
         const int r2 = maps.rowmap2[upos[wg0]];
         d2.on = r2 >= 0;
@@ -1057,6 +1065,7 @@ __device__ __forceinline__ bool apply_body_impl(
                       ? maps.push_tab + static_cast<uint64_t>(static_cast<uint32_t>(pit.y)) * static_cast<uint64_t>(width)
                       : nullptr;
         d2.push2 = (pit.z & kPosVictimPush) ? dst + static_cast<uint64_t>(*maps.victim_row) * static_cast<uint64_t>(width) : nullptr;
+        d2.keep = (pit.z & kPosKeep) != 0;
     } else if (DUAL && maps.rowmap2) {
         const int r2 = maps.rowmap2[upos[p]];
         d2.on = r2 >= 0;

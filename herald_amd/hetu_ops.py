@@ -132,6 +132,7 @@ class ParameterServerCommunicateOp:
         self.peek_ids = peek_ids
         self._peek_offset = 1
         self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
+        self._chain = False           # the planned flow of the asp schedule: _planned = ids of a push-pull chain's batches
 
     def forward_hook(self, config, first_ids=None, barrier=lambda: None):   # :130-242
         self.config, self.barrier = config, barrier
@@ -172,6 +173,11 @@ class ParameterServerCommunicateOp:
                     self._planned = []        # pull(k + 1) follows push(k) of the same ids batch after batch: the planned pairs
             elif config.prefetch:
                 self.compute = self._compute_asp_prefetch
+                if getattr(config, "cache_plan_ahead", False) and store.world == 1 and self.peek_ids is not None and \
+                        config.cstable_policy.lower() == "lru":
+                    # every step is ONE cache call, push_pull(pull = batch k + 1, push = batch k): the planned push-pull chain
+                    # (LRU; LFU / LFUOpt keep the call-by-call embedding_push_pull)
+                    self._planned, self._chain = [], True
             else:
                 self.compute = self._compute_no_prefetch
         else:
@@ -265,6 +271,18 @@ class ParameterServerCommunicateOp:
 
     def _pull_cache(self, ids):
         dest = self.sparse_pull_val.reshape(-1, self.parameter.shape[1])
+        if self._chain:
+            # the chain's head (the first prefetch): this batch and the next one are planned, this one is looked up
+            if isinstance(ids, tuple):
+                raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): push plans (laia) are not part of the "
+                                   "planned push-pull chain")
+            if self._planned:
+                raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): only the first pull is a plain lookup")
+            self._plan_chain(ids)
+            nxt = self.peek_ids(self._peek_offset)
+            if nxt is not None:
+                self._plan_chain(nxt)
+            return self.cache.embedding_lookup_planned(dest)
         if self._planned is not None:
             if not self._planned:                                  # the first pull: nothing planned yet
                 self._plan(ids)
@@ -282,7 +300,40 @@ class ParameterServerCommunicateOp:
             ids = ids[0]
         return self.cache.embedding_lookup(ids.reshape(-1), dest)
 
+    def _plan_chain(self, ids):
+        if isinstance(ids, tuple):
+            raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): push plans (laia) are not part of the "
+                               "planned push-pull chain")
+        ids = ids.reshape(-1)
+        self.cache.plan_block([ids], push_pull=True)
+        self._planned.append(ids)
+
+    def _push_pull_planned(self, grad):
+        """One step of the planned push-pull chain: the gradients are those of the batch pulled last, the batch after next is
+        planned from peek_ids (its bookkeeping runs beside this step's rows and the model), ONE cache call."""
+        if grad.push_indices is not None:
+            raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): gradients with push_indices (laia push "
+                               "plans) are not part of the planned push-pull chain; use bsp=0 or cache_plan_ahead=False")
+        if not self._planned or not _same_tensor(self._planned[0], grad.indices.reshape(-1)):
+            raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): the gradients pushed are not those of the "
+                               "batch pulled last")
+        nxt = self.next_ids()
+        if len(self._planned) < 2:                                 # peek_ids had run dry: the step is planned now
+            self._plan_chain(nxt)
+        elif isinstance(nxt, tuple) or not _same_tensor(self._planned[1], nxt.reshape(-1)):
+            raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): the batch to pull is not the one "
+                               "peek_ids announced")
+        after = self.peek_ids(1)
+        if after is not None:
+            self._plan_chain(after)
+        self._planned.pop(0)
+        width = self.parameter.shape[1]
+        return self.cache.embedding_push_pull_planned(self.sparse_pull_val.reshape(-1, width),
+                                                      grad.values.reshape(-1, width).contiguous())
+
     def _push_pull_cache(self, grad):
+        if self._chain:
+            return self._push_pull_planned(grad)
         nxt = self.next_ids()
         return self.cache.embedding_push_pull((nxt[0] if isinstance(nxt, tuple) else nxt).reshape(-1),
                                               self.sparse_pull_val.reshape(-1, self.parameter.shape[1]),

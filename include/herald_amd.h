@@ -942,6 +942,38 @@ int ha_cache_plan_pending(ha_cache *cache);
 /* `count` planned pairs by one call: ha_cache_lookup_planned(n[k], dests[k]) then ha_cache_update_planned(n[k], grads[k]) */
 int ha_cache_run_planned_pairs(ha_cache *cache, int count, const int64_t *n, float *const *dests, const float *const *grads,
                                ha_stream_t stream);
+/* The planned flow of a PUSH-PULL CHAIN: CacheBase::_embeddingPushPull (cache.cc:356-422), the one cache call per step of the
+ * asp-with-prefetch schedule (python/hetu/gpu_ops/ParameterServerCommunicate.py:37-40, 68-72): step = push_pull(pull = the ids of
+ * batch k + 1, push = the ids and gradients of batch k).  LRU over a local store only (the LFU policies' planned bookkeeping
+ * rests on lookup + update pairs; they keep ha_cache_push_pull).  A block is 1..16 entries; entry i's step pulls batch i
+ * (keys[i], n[i] >= 0 keys) and pushes the batch of the entry before it in the chain, across block boundaries.  The chain's
+ * FIRST entry has nothing to push: its step is a plain _embeddingLookup (:60-107), made by ha_cache_lookup_planned.  An entry
+ * with n[i] < 0, allowed as the LAST entry of a block only, CLOSES the chain: its step pulls nothing and is a plain
+ * _embeddingUpdate (:132-197) of the batch pulled last, made by ha_cache_update_planned(n of that batch, grads).  Every other
+ * step is ha_cache_push_pull_planned.  A call that is not the one due is refused and changes nothing; ha_cache_plan_pending
+ * counts ONE call per entry.
+ * Required, and checked before anything is enqueued: n_pull + n_push <= limit for every step (then no line that a step touches
+ * is evicted by the step's own insert, and every push key is still resident); a chain starts from a cache with no planned call
+ * outstanding and no pending evicted line; pair blocks (ha_cache_plan_block*) are refused while a chain is open.  Keys beyond
+ * the cache's range give zeros on the pull side and are ignored on the push side, as in the pair flow.
+ * The bookkeeping of the block (one launch, cache_book_chain_kernel: the reference's order of touches -- pull hits, push keys,
+ * inserted misses --, slots, evictions, counters, the bounded push) runs on `side`, ALWAYS ordered behind everything enqueued
+ * on `main` so far (as ha_cache_plan_block_push_keys).  The dirty lines a step's insert evicts wait for the NEXT step's push
+ * (cache.cc:378), so between two steps ha_cache_state reports them as pending.  A step's row work is two launches on the row
+ * stream and no bookkeeping: the push half (ordered accumulate, pushed and evicted lines' store rows, versions) and the pull
+ * half, which judges staleness with the line's version as it was before the push half's commit (cache.cc:404 against :414-421:
+ * a line pushed with more than pull_bound updates is pulled back at once, and Line::addup still adds its gradient).
+ * While a chain is open and no planned call is outstanding, the call-by-call entry points are refused: close the chain first
+ * (plan a block whose only entry is the closing one, then ha_cache_update_planned).  After the closing step the cache is in
+ * the state call-by-call code expects.  Results: those of ha_cache_lookup, ha_cache_push_pull ..., ha_cache_update call by call
+ * (tests/test_gpu_cache_planned_push_pull.py holds both to oracle/cache_model.py). */
+int ha_cache_plan_block_push_pull(ha_cache *cache, const void *const *keys, int key_kind, const int64_t *n, int count,
+                                  ha_stream_t side, ha_stream_t main);
+int ha_cache_push_pull_planned(ha_cache *cache, int64_t n_pull, float *dest, int64_t n_push, const float *grads,
+                               ha_stream_t stream);
+/* `count` middle steps of a chain by one call: ha_cache_push_pull_planned(n_pull[k], dests[k], n_push[k], grads[k]) */
+int ha_cache_run_planned_push_pulls(ha_cache *cache, int count, const int64_t *n_pull, float *const *dests,
+                                    const int64_t *n_push, const float *const *grads, ha_stream_t stream);
 int ha_cache_update(ha_cache *cache, const void *keys, int key_kind, int64_t n,
                     const float *grads, ha_stream_t stream);
 /* ha_cache_update for the key batch of the immediately preceding ha_cache_lookup on this cache (the
