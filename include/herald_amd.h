@@ -107,7 +107,10 @@ int SGDOptimizerSparseUpdate(DLArrayHandle param,
                              DLStreamHandle stream_handle);
 
 /* Sparse optimizers on DEDUPLICATED indices (callers run IndexedSlices.deduplicate first,
- * python/hetu/gpu_links/OptimizerLink.py:60,78,95):
+ * python/hetu/gpu_links/OptimizerLink.py:60,78,95).  For all of the optimizer symbols below: an index at or
+ * beyond the number of rows is skipped; negative and NaN indices are outside the contract (the conversion is
+ * static_cast<uint32_t>(float), undefined for them).  Arrays need not be 16-byte aligned.  A call whose arguments are
+ * refused (-1) has enqueued nothing and changes nothing.
  * src/common/c_runtime_api.h:661-664 / src/ops/OptimizersSparse.cu:331-389 */
 int AdaGradOptimizerSparseUpdate(DLArrayHandle param,
                                  const DLArrayHandle grad_indices,
@@ -141,7 +144,7 @@ int AddL2RegularizationSparse(const DLArrayHandle param,
  * (OptimizerLink.py:37-49 does not deduplicate).  velocity[id,:] += -lr*g per occurrence (Nesterov: the
  * parameter row too), in occurrence order instead of the reference's atomics; then the reference's DENSE
  * second phase over the whole array: param += velocity, velocity *= momentum (Nesterov: velocity *=
- * momentum first, then param += velocity). */
+ * momentum first, then param += velocity).  With no indices (n = 0) the dense phase still runs. */
 int MomentumOptimizerSparseUpdate(DLArrayHandle param,
                                   const DLArrayHandle grad_indices,
                                   const DLArrayHandle grad_values,

@@ -195,7 +195,7 @@ def momentum_sparse(param, veloc, ids, grads, lr, momentum, nesterov):
     reference's float atomics pick an arbitrary one); second phase DENSE over the whole arrays.  In place."""
     f = np.float32
     idx = np.asarray(ids).astype(np.int64).reshape(-1)
-    g = np.asarray(grads, dtype=f).reshape(idx.size, -1)
+    g = np.asarray(grads, dtype=f).reshape(idx.size, param.shape[1])     # n = 0: the dense phase alone
     for i, r in enumerate(idx):
         t = (-f(lr) * g[i]).astype(f)
         veloc[r] = (veloc[r] + t).astype(f)

@@ -69,8 +69,9 @@ def _dedup_case(dev, seed, rows, width, n):
 
 @pytest.mark.parametrize("rows,width,n", [(500, 400, 100), (300, 7, 64), (2000, 512, 1500), (50, 1030, 20)])
 def test_sparse_optimizers_every_width_path(dev, rows, width, n):
-    """16-byte vector path (width % 4 == 0), scalar path (width 7), wide rows, more rows than one pass of
-    the grid: AdaGrad, Adam, AdamW and sparse L2 against the numpy oracle."""
+    """16-byte vector path (width % 4 == 0), scalar path (width 7), wide rows (1030: several column trips), 1,500
+    rows (still ONE pass of the grid: a second one needs more than 16,384 x 4 rows, test_gpu_optim_paths.py):
+    AdaGrad, Adam, AdamW and sparse L2 against the numpy oracle."""
     param, uniq, red = _dedup_case(dev, rows + width, rows, width, n)
     d_ids, d_red = torch.from_numpy(uniq).to(dev), torch.from_numpy(red).to(dev)
     # sparse L2 (OptimizerLink.py:8-21): grads += l2reg * param[ids]
@@ -234,3 +235,4 @@ def test_fused_dedup_plus_optimizer_equals_the_two_step_sequence(dev, kind, rows
                         0.01 if kind == "adamw" else None)
     np.testing.assert_allclose(fp.cpu().numpy(), param, **TOL)
     np.testing.assert_allclose(f1.cpu().numpy(), s1, **TOL)
+    np.testing.assert_allclose(f2.cpu().numpy(), s2, **TOL)     # AdaGrad has no second state: s2 stays zero
