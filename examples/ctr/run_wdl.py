@@ -32,6 +32,11 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      the dense tower's gradients are all-reduced (Hybrid).  torchrun for N > 1.  With
                      --cache-planned on one rank the cache runs its planned flow: the batch after next and its plan are
                      booked ahead (LAIADataloader.peek_arr), every lookup and every push-plan update is one launch.
+  --model emb_sum_wdl  the pooled Wide & Deep (examples/ctr/models/emb_sum_wdl_criteo.py): a sample's 26 rows are summed into one
+                     before the tower (embedding_lookup_op + reduce_sum_op(axes=1)).  --embedding hbm: the fused sum-pooled
+                     lookup (ha_gather_sum_*) and the bag apply (ha_sgd_apply_bags) -- neither [B, 26, d] nor the expanded
+                     gradient is built; ps / cache: per-occurrence rows as before, summed in the same order, the pooled
+                     gradient expanded before the push.  The step engines refuse the model.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -102,8 +107,21 @@ class CrossTower(torch.nn.Module):
         return torch.sigmoid(torch.cat([x1, y3], dim=1) @ self.W4)
 
 
+class SumTower(Tower):
+    """The dense part of emb_sum_wdl_criteo (models/emb_sum_wdl_criteo.py:18-35): the 26 embedding rows of a sample arrive
+    summed into one, so W4 is [256 + width, 1] and y4 = cat(pooled, y3)."""
+
+    def __init__(self, width, seed=0):
+        super().__init__(width, seed)
+        g = torch.Generator().manual_seed(seed + 4)
+        self.W4 = torch.nn.Parameter(torch.randn(256 + width, 1, generator=g) * 0.01)
+
+
+POOLED_MODELS = ("emb_sum_wdl",)
+
+
 def make_tower(model, width, seed=0):
-    return {"wdl": Tower, "dcn": CrossTower}[model](width, seed)
+    return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower}[model](width, seed)
 
 
 def make_samples(nsamples, rows, seed=0):
@@ -230,6 +248,11 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
     replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests)."""
     dev = torch.device(device)
+    pooled = model in POOLED_MODELS
+    if pooled and embedding in ("step", "step3", "queue"):
+        raise ValueError("--model %s pools its embeddings (sum over a sample's 26 rows): the step engines (--embedding step, "
+                         "step3, queue) deliver and update per-occurrence rows only; use --embedding hbm (fused), ps or cache"
+                         % model)
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
@@ -265,9 +288,15 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                                      peek_ids=lambda j: ids_of(state["k"] + 1 + j))
         barrier = dist.barrier if world > 1 else (lambda: None)
         comm.forward_hook(config, first_ids=ids_of(0), barrier=barrier)
-    lookup = hetu_ops.EmbeddingLookUp(param)
+    if pooled:
+        # embedding_lookup_op + reduce_sum_op(axes=1) as one operator: the fused kernel on a device table, the same ordered sum
+        # over the delivered rows on the ps / cache paths; its gradient stays [batch, width] (pooled IndexedSlices)
+        lookup = hetu_ops.EmbeddingLookUpSum(param)
+        lookup_grad = hetu_ops.EmbeddingLookUpSum_Gradient(param.shape)
+    else:
+        lookup = hetu_ops.EmbeddingLookUp(param)
+        lookup_grad = hetu_ops.EmbeddingLookUp_Gradient(param.shape)
     lookup.forward_hook(config)
-    lookup_grad = hetu_ops.EmbeddingLookUp_Gradient(param.shape)
 
     fused = None
     if embedding == "step":
@@ -302,10 +331,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
         elif fused is not None:
             emb = fused["outs"][k % 2].detach().clone()            # looked up by the previous step's launch
         else:
-            emb = torch.empty((batch, NFIELD, width), dtype=torch.float32, device=dev)
-            lookup.compute(ids, emb)                               # embedding_lookup_op
+            emb = torch.empty((batch, width) if pooled else (batch, NFIELD, width), dtype=torch.float32, device=dev)
+            lookup.compute(ids, emb)                               # embedding_lookup_op (+ reduce_sum_op(axes=1))
         emb.requires_grad_(True)
-        pred = tower(dense, emb.reshape(batch, NFIELD * width))
+        pred = tower(dense, emb.reshape(batch, -1))
         loss = torch.nn.functional.binary_cross_entropy(pred, label)
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -372,7 +401,8 @@ def main():
     # --comm / --cache choose the embedding engine unless --embedding names one (this build's own engines: the HBM-resident
     # table with one launch per step, "queue" = the work-queue step with lookahead, ...).
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo (the reference's names) or wdl | dcn")
+    ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo (the reference's names) or "
+                                                   "wdl | dcn | emb_sum_wdl")
     ap.add_argument("-b", "--batch-size", "--batch", dest="batch", type=int, default=256)
     ap.add_argument("-e", "--embedding-size", "--width", dest="width", type=int, default=128)
     ap.add_argument("-r", "--cache-limit-ratio", type=float, default=0.1,
@@ -400,10 +430,13 @@ def main():
     ap.add_argument("--laia", action="store_true", help="the laia-scheduled loop of run_laia.py (cache over the sharded table)")
     ap.add_argument("--local-shared", action="store_true", help="--laia with the TopkScheduler + shared-memory rings")
     args = ap.parse_args()
-    model = args.model.split("_")[0]
-    if model not in ("wdl", "dcn"):
-        ap.error("--model must be wdl_criteo, dcn_criteo, wdl or dcn")
+    model = args.model[:-len("_criteo")] if args.model.endswith("_criteo") else args.model
+    if model not in ("wdl", "dcn") + POOLED_MODELS:
+        ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, wdl, dcn or emb_sum_wdl")
     args.model = model
+    if model in POOLED_MODELS and (args.laia or args.embedding in ("step", "step3", "queue")):
+        ap.error("--model %s pools its embeddings: use --embedding hbm (the fused kernel), ps or cache; the step engines "
+                 "(step, step3, queue) and --laia run per-occurrence models only" % model)
     comm = None if args.comm in (None, "None") else args.comm
     if comm not in (None, "PS", "Hybrid"):
         ap.error("--comm must be None, PS or Hybrid (dense AllReduce-only runs have no sparse path to replace)")

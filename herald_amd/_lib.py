@@ -210,6 +210,13 @@ def _declare(L):
         "ha_sgd_apply_finished": [vp, i64, i64, vp, i64, vp, f32, vp],
         "ha_push_apply": [vp, i64, i64, vp, i64, vp, vp],
         "ha_sgd_sparse_update_f32ids": [vp, i64, i64, vp, i64, vp, f32, vp],
+        "ha_gather_sum_f32ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp],
+        "ha_gather_sum_u64ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp],
+        "ha_bag_of": [vp, i64, i64, vp, vp],
+        "ha_sgd_apply_bags": [vp, i64, i64, vp, i64, vp, i64, vp, f32, vp],
+        "ha_sgd_sparse_update_bags_f32ids": [vp, i64, i64, vp, i64, vp, i64, vp, i64, f32, vp],
+        "ha_sgd_sparse_update_bags_u64ids": [vp, i64, i64, vp, i64, vp, i64, vp, i64, f32, vp],
+        "ha_debug_bag_slice": [c.c_int],
         "ha_lookup_sort_f32ids": [vp, i64, i64, vp, i64, vp, vp, vp],
         "ha_lookup_sort_u64ids": [vp, i64, i64, vp, i64, vp, vp, vp],
         "ha_sgd_apply_finish": [vp, i64, i64, vp, i64, vp, f32, vp],

@@ -1,0 +1,270 @@
+// Sum-pooled embedding lookup ("EmbeddingBag", sum mode): out[b,:] = ((0.0f + r_0) + r_1) + ... + r_{m-1} over the table rows
+// r_j of bag b's ids, in position order, one __fadd_rn per term.
+//
+// Replaces the pair embedding_lookup_op + reduce_sum_op(axes=1) of the reference's pooled CTR models
+// (examples/ctr/models/emb_sum_wdl_criteo.py:14-16): the per-occurrence tensor [B, F, d] is never written.  The reference's
+// reduction order is cuDNN's / numpy's and specified nowhere; the fixed order here makes the result reproducible and equal on
+// every path of this project.  An id >= rows contributes a zero row (as the gather, gather_dev.h); an empty bag gives zeros.
+//
+// Bags.  Fixed: ids is [nbags, bag], occurrence i belongs to bag i / bag.  Ragged: offsets[nbags + 1] (int64, offsets[0] = 0,
+// offsets[nbags] = n, non-decreasing); every offset is clamped to [0, n] and every bag's end to its start, so no id at or beyond
+// n is read and no output row at or beyond nbags written, whatever offsets holds.
+//
+// MI355X layout.  One wave per (bag, column slice): the sum of a bag is an ordered chain per column, so a bag is split over waves
+// by COLUMNS only (a 256-bag batch of 512-float rows would otherwise leave the chip nearly empty).  A wave fetches its bag's ids
+// once -- lane l holds id l of the current block of 64 -- and broadcasts the row numbers with v_readlane; the row loads are
+// branch-free (clamped addresses, see gather_dev.h) and ROWS of them are in flight before the first add.  The slice is 64 * VEC
+// floats: VEC = 1 (256 bytes of a row per request, also the path of any width / alignment), 2 or 4 (1 KiB per request).
+// Slices of one bag are adjacent waves, so its ids are served by the L1 / L2 after the first of them.
+//
+// Algorithmic bytes: n * (4 * width + 4) read + nbags * 4 * width written.
+#include "gather_dev.h"
+
+namespace ha {
+
+template <int VEC>
+struct BagVec;
+template <>
+struct BagVec<1> {
+    typedef float T;
+    static __device__ __forceinline__ float get(const T &v, int) { return v; }
+    static __device__ __forceinline__ void set(T &v, int, float x) { v = x; }
+};
+template <>
+struct BagVec<2> {
+    typedef float T __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
+    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
+};
+template <>
+struct BagVec<4> {
+    typedef float4v T;
+    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
+    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
+};
+
+constexpr int kBagWaves = 4;   // waves per workgroup
+
+// ROWS: table rows requested per round (all in flight before the first add).
+template <typename IdT, int VEC, int ROWS>
+__global__ __launch_bounds__(kBagWaves *kWave) void bag_sum_kernel(
+    const float *__restrict__ table, uint64_t rows, uint32_t width, const IdT *__restrict__ ids, int64_t n, int64_t bag,
+    const int64_t *__restrict__ offsets, int64_t nbags, uint32_t nslice, float *__restrict__ out) {
+    typedef typename BagVec<VEC>::T V;
+    const int lane = lane_id();
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kBagWaves + (threadIdx.x >> 6);   // wave-uniform
+    if (item >= static_cast<uint64_t>(nbags) * nslice)
+        return;
+    const int64_t b = static_cast<int64_t>(item / nslice);
+    const uint32_t sl = static_cast<uint32_t>(item - static_cast<uint64_t>(b) * nslice);
+    int64_t lo, hi;
+    if (offsets != nullptr) {
+        lo = offsets[b];
+        hi = offsets[b + 1];
+        lo = lo < 0 ? 0 : (lo > n ? n : lo);
+        hi = hi < lo ? lo : (hi > n ? n : hi);
+    } else {
+        lo = b * bag;
+        hi = lo + bag;      // (n == nbags * bag: checked by the host)
+    }
+    const uint32_t col = (sl * kWave + lane) * VEC;
+    const bool live = col < width;       // (VEC > 1: width % VEC == 0, so a live lane's VEC columns all exist)
+    const uint32_t lcol = live ? col : 0;
+    V acc;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+        BagVec<VEC>::set(acc, k, 0.f);
+    for (int64_t j0 = lo; j0 < hi; j0 += kWave) {
+        const int cnt = static_cast<int>(hi - j0 < kWave ? hi - j0 : kWave);      // ids of this block (wave-uniform)
+        const int64_t j = j0 + (lane < cnt ? lane : cnt - 1);                      // lo <= j < hi <= n
+        const uint64_t r = id_to_row<IdT>(ids[j]);
+        const bool ok = r < rows;
+        const unsigned long long okm = __ballot(ok);
+        const uint64_t off = (ok ? r : 0) * width;          // float offset of the row (row 0 for an id beyond the table)
+        const int off_lo = static_cast<int>(static_cast<uint32_t>(off));
+        const int off_hi = static_cast<int>(static_cast<uint32_t>(off >> 32));
+        for (int c = 0; c < cnt; c += ROWS) {
+            V v[ROWS];
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const int tt = c + t < cnt ? c + t : cnt - 1;
+                const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(off_hi, tt))) << 32) |
+                                   static_cast<uint32_t>(__builtin_amdgcn_readlane(off_lo, tt));
+                v[t] = *reinterpret_cast<const V *>(table + o + lcol);
+            }
+            // every request of the round is issued before the first add: the scheduler would otherwise interleave them (about ten
+            // rows in flight instead of ROWS, three round trips for a bag of 26 instead of one)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const bool in = c + t < cnt;                                  // wave-uniform
+                const bool rok = ((okm >> (in ? c + t : 0)) & 1ull) != 0;     // an id beyond the table adds a zero row
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float a = BagVec<VEC>::get(acc, k);
+                    const float s = __fadd_rn(a, rok ? BagVec<VEC>::get(v[t], k) : 0.f);
+                    BagVec<VEC>::set(acc, k, in ? s : a);
+                }
+            }
+        }
+    }
+    // the pooled rows are consumed by another kernel (the dense tower): written around the L2, as the gather's
+    if (live)
+        __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
+}
+
+// bag_of[i] = the bag of occurrence i: the largest b in [0, nbags) with offsets[b] <= i (empty bags are skipped).  Always in
+// [0, nbags), whatever offsets holds; offsets[0] and offsets[nbags] are not read.
+__global__ __launch_bounds__(256) void bag_of_kernel(const int64_t *__restrict__ offsets, int nbags, int64_t n,
+                                                     int32_t *__restrict__ bag_of) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    int lo = 0, hi = nbags;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    bag_of[i] = lo;
+}
+
+// Slice width of the 16-byte path in floats: 0 = by the rule in bag_sum_launch, else 64 / 128 / 256 (ha_debug_bag_slice).
+static int g_bag_slice = 0;
+
+template <typename IdT>
+static int bag_sum_launch(const char *what, const float *table, int64_t rows, int64_t width, const IdT *ids, int64_t n,
+                          int64_t bag, const int64_t *offsets, int64_t nbags, float *out, hipStream_t stream) {
+    HA_REQUIRE(rows >= 0 && width >= 1 && width < (1ll << 30) && n >= 0 && nbags >= 0 && bag >= 0,
+               "%s: bad sizes rows=%ld width=%ld n=%ld bag=%ld nbags=%ld", what, (long)rows, (long)width, (long)n, (long)bag,
+               (long)nbags);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld, offsets %s)", what,
+               (long)bag, offsets ? "given" : "null");
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+               (long)n, (long)nbags, (long)bag);
+    if (nbags == 0)
+        return 0;
+    HA_REQUIRE(table != nullptr, "%s: null table", what);
+    HA_REQUIRE(out != nullptr && (ids != nullptr || n == 0), "%s: null pointer", what);
+    if (rows == 0) {      // every id is beyond the table (and there is no row 0 for the clamped loads to read)
+        HA_CHECK_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(nbags) * width * sizeof(float), stream));
+        return 0;
+    }
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    // Slice of the 16-byte path: the widest one that is no wider than a row and still gives the chip 8 waves per compute unit
+    // (2,048 waves); batches too small for that take 64-float slices.  (256 bags of 26 x 512 floats: 2,048 waves of 64 floats;
+    // 4,096 bags of 128 floats: 4,096 waves of 128 floats.  Not measured yet: docs/EXPERIMENTS.md round 6 section 18.)
+    int vec = 1;
+    if (vec_ok) {
+        if (g_bag_slice != 0) {
+            vec = g_bag_slice / kWave;
+        } else {
+            for (vec = 4; vec > 1; vec >>= 1)
+                if (kWave * vec <= width && nbags * ((width + kWave * vec - 1) / (kWave * vec)) >= 2048)
+                    break;
+        }
+    }
+    const uint32_t nslice = static_cast<uint32_t>((width + kWave * vec - 1) / (kWave * vec));
+    const uint64_t blocks64 = (static_cast<uint64_t>(nbags) * nslice + kBagWaves - 1) / kBagWaves;
+    HA_REQUIRE(blocks64 < (1ull << 31), "%s: batch too large", what);
+    // rows per round by the (mean) bag size: a bag of 26 is one round of 32 requests
+    const int64_t mean = offsets ? (n + nbags - 1) / nbags : bag;
+    const bool few = mean <= 8;
+    const dim3 grid(static_cast<unsigned>(blocks64)), block(kBagWaves * kWave);
+#define HA_BAG_CASE(V, R)                                                                                               \
+    hipLaunchKernelGGL((bag_sum_kernel<IdT, V, R>), grid, block, 0, stream, table, (uint64_t)rows, (uint32_t)width, ids, n, \
+                       bag, offsets, nbags, nslice, out)
+    if (vec == 4) {
+        if (few) HA_BAG_CASE(4, 8); else HA_BAG_CASE(4, 32);
+    } else if (vec == 2) {
+        if (few) HA_BAG_CASE(2, 8); else HA_BAG_CASE(2, 32);
+    } else {
+        if (few) HA_BAG_CASE(1, 8); else HA_BAG_CASE(1, 32);
+    }
+#undef HA_BAG_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+int scratch_get(hipStream_t stream, size_t bytes, void **out);   // capi.hip
+
+template <typename IdT>
+static int sgd_sparse_update_bags(const char *what, float *table, int64_t rows, int64_t width, const IdT *ids, int64_t n,
+                                  const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags, float lr,
+                                  ha_stream_t stream) {
+    HA_REQUIRE(rows >= 0 && width >= 1 && width < (1ll << 30) && n >= 0 && n < (1ll << 31) && nbags >= 0 && bag >= 0 &&
+                   nbags < (1ll << 31),
+               "%s: bad sizes rows=%ld width=%ld n=%ld bag=%ld nbags=%ld", what, (long)rows, (long)width, (long)n, (long)bag,
+               (long)nbags);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld)", what, (long)bag);
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+               (long)n, (long)nbags, (long)bag);
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(table && ids && bag_grads && nbags >= 1, "%s: null pointer or no bags", what);
+    const size_t plan_bytes = align_up(ha_plan_bytes(n), 256);
+    void *ws = nullptr;
+    if (scratch_get(as_stream(stream), plan_bytes + (offsets ? static_cast<size_t>(n) * 4 : 0), &ws))
+        return -1;
+    int32_t *bag_of = nullptr;
+    if (offsets) {
+        bag_of = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + plan_bytes);
+        if (ha_bag_of(offsets, nbags, n, bag_of, stream))
+            return -1;
+    }
+    if (sizeof(IdT) == 4 ? ha_plan_sort_f32ids(reinterpret_cast<const float *>(ids), n, ws, stream)
+                         : ha_plan_sort_u64ids(reinterpret_cast<const uint64_t *>(ids), n, ws, stream))
+        return -1;
+    return ha_sgd_apply_bags(table, rows, width, ws, n, bag_grads, offsets ? 0 : bag, bag_of, lr, stream);
+}
+
+}  // namespace ha
+
+extern "C" int ha_gather_sum_f32ids(const float *table, int64_t rows, int64_t width, const float *ids, int64_t n, int64_t bag,
+                                    const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream) {
+    return ha::bag_sum_launch<float>("ha_gather_sum_f32ids", table, rows, width, ids, n, bag, offsets, nbags, out,
+                                     ha::as_stream(stream));
+}
+
+extern "C" int ha_gather_sum_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
+                                    const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream) {
+    return ha::bag_sum_launch<uint64_t>("ha_gather_sum_u64ids", table, rows, width, ids, n, bag, offsets, nbags, out,
+                                        ha::as_stream(stream));
+}
+
+extern "C" int ha_bag_of(const int64_t *offsets, int64_t nbags, int64_t n, int32_t *bag_of, ha_stream_t stream) {
+    HA_REQUIRE(nbags >= 0 && n >= 0 && nbags < (1ll << 31) && n < (1ll << 31), "ha_bag_of: bad sizes nbags=%ld n=%ld",
+               (long)nbags, (long)n);
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(nbags >= 1, "ha_bag_of: %ld ids in no bag", (long)n);
+    HA_REQUIRE(offsets && bag_of, "ha_bag_of: null pointer");
+    hipLaunchKernelGGL(ha::bag_of_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, ha::as_stream(stream),
+                       offsets, static_cast<int>(nbags), n, bag_of);
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ha_sgd_sparse_update_bags_f32ids(float *table, int64_t rows, int64_t width, const float *ids, int64_t n,
+                                                const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                                float lr, ha_stream_t stream) {
+    return ha::sgd_sparse_update_bags<float>("ha_sgd_sparse_update_bags_f32ids", table, rows, width, ids, n, bag_grads, bag,
+                                             offsets, nbags, lr, stream);
+}
+
+extern "C" int ha_sgd_sparse_update_bags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n,
+                                                const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                                float lr, ha_stream_t stream) {
+    return ha::sgd_sparse_update_bags<uint64_t>("ha_sgd_sparse_update_bags_u64ids", table, rows, width, ids, n, bag_grads, bag,
+                                                offsets, nbags, lr, stream);
+}
+
+extern "C" int ha_debug_bag_slice(int floats) {
+    HA_REQUIRE(floats == 0 || floats == 64 || floats == 128 || floats == 256,
+               "ha_debug_bag_slice: 0 (automatic), 64, 128 or 256 floats");
+    ha::g_bag_slice = floats;
+    return 0;
+}

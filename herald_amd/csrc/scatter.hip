@@ -54,6 +54,22 @@ __global__ __launch_bounds__(1024, 8) void apply_mapped_kernel(
     apply_body<kModeSgd, VEC>(dst, dst_rows, width, sorted, perm, upos, n, src, lr, blockIdx.x, s_apply, nullptr, maps);
 }
 
+// pooled gradients (sum-pooled lookup, bagsum.hip): the gradient row of occurrence i is the row of its bag -- i / bag for
+// fixed bags (in registers, no map read), bag_of[i] for ragged ones.  The body is apply_kernel's.
+template <int VEC, bool FIXED>
+__global__ __launch_bounds__(1024, 8) void apply_bags_kernel(
+    float *__restrict__ dst, uint64_t dst_rows, int width,
+    const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
+    const int32_t *__restrict__ upos, int n, const float *__restrict__ bag_grads,
+    float lr, int tree_from, int bag, const int32_t *__restrict__ bag_of) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
+    ApplyMaps maps{};
+    maps.tree_from = tree_from;
+    maps.valmap = FIXED ? nullptr : bag_of;
+    maps.valdiv = FIXED ? bag : 0;
+    apply_body<kModeSgd, VEC, false, kHandNone, true>(dst, dst_rows, width, sorted, perm, upos, n, bag_grads, lr, blockIdx.x, s_apply, nullptr, maps);
+}
+
 // two destinations, one pass (the cache's Line::accumulate: gradient buffer and data row)
 template <int VEC>
 __global__ __launch_bounds__(1024, 8) void apply_mapped2_kernel(
@@ -620,6 +636,50 @@ extern "C" int ha_sgd_apply(float *table, int64_t rows, int64_t width,
                             float lr, ha_stream_t stream) {
     return ha::apply_launch<ha::kModeSgd>(table, rows, width, plan_ws, n, grads,
                                           lr, ha::as_stream(stream));
+}
+
+// ha_sgd_apply on the gradient of a sum-pooled lookup (ha_gather_sum_*): table[key,:] -= lr * bag_grads[bag_of(i),:] for every
+// occurrence i, in occurrence order -- what ha_sgd_apply gives on bag_grads expanded to [n, width], and what ha_apply_mapped
+// gives with valmap = bag_of, bit for bit (tolerance mode included: the same runs take the same tree over the same values).
+// One wave per sorted position whatever n is; the plan needs to be sorted only.
+extern "C" int ha_sgd_apply_bags(float *table, int64_t rows, int64_t width, const void *plan_ws, int64_t n,
+                                 const float *bag_grads, int64_t bag, const int32_t *bag_of, float lr, ha_stream_t stream) {
+    using namespace ha;
+    HA_REQUIRE(n >= 0 && rows >= 0 && width >= 1 && width < (1 << 30) && n < (1ll << 31), "ha_sgd_apply_bags: bad sizes");
+    HA_REQUIRE((bag >= 1) != (bag_of != nullptr), "ha_sgd_apply_bags: give exactly one of bag >= 1 and bag_of (bag=%ld)",
+               (long)bag);
+    HA_REQUIRE(bag_of != nullptr || (bag < (1ll << 31) && n % bag == 0), "ha_sgd_apply_bags: n=%ld is not a multiple of bag=%ld",
+               (long)n, (long)bag);
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(table && plan_ws && bag_grads, "ha_sgd_apply_bags: null pointer");
+    ha_plan_view v;
+    if (ha_plan_view_of(const_cast<void *>(plan_ws), n, &v) != 0)
+        return -1;
+    const unsigned blocks = static_cast<unsigned>((n + kPosPerBlock - 1) / kPosPerBlock);
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(bag_grads) % 16 == 0);
+    const bool fixed = bag_of == nullptr;
+    static DeviceOnce lds_allowed;
+    if (lds_allowed.run([]() -> int {
+            HA_ALLOW_LDS((apply_bags_kernel<4, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_bags_kernel<4, false>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_bags_kernel<1, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_bags_kernel<1, false>), kApplyLdsBytes);
+            return 0;
+        }))
+        return -1;
+#define HA_BAGS_CASE(V, F)                                                                                               \
+    hipLaunchKernelGGL((apply_bags_kernel<V, F>), dim3(blocks), dim3(1024), kApplyLdsBytes, as_stream(stream), table,    \
+                       (uint64_t)rows, (int)width, v.sorted, v.perm, v.upos, (int)n, bag_grads, lr,                      \
+                       tolerance_tree_from(), (int)bag, bag_of)
+    if (vec_ok && fixed) HA_BAGS_CASE(4, true);
+    else if (vec_ok) HA_BAGS_CASE(4, false);
+    else if (fixed) HA_BAGS_CASE(1, true);
+    else HA_BAGS_CASE(1, false);
+#undef HA_BAGS_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
 }
 
 // ha_sgd_apply for a FINISHED plan (ha_plan_build_*, or ha_plan_sort_* + ha_plan_finish): batches of more than 36,864 ids

@@ -50,7 +50,15 @@ struct ApplyMaps {
     // kPosKeep (a planned push-pull step): the pushed line is pulled in the same step, and Line::addup of that pull still sees
     // the gradient (cache.cc:404 runs in front of zeroGrad, :419) -- the first destination keeps its new value instead of zeros
     const int *victim_row;
+    // pooled gradients (sum-pooled lookup, bagsum.hip; BAGS kernels only, every other kernel ignores it): fixed bags of
+    // `valdiv` ids -- the source row of occurrence i is i / valdiv, computed in registers (0 = none; ragged bags give their
+    // bag_of[n] as valmap instead)
+    int valdiv;
 };
+// source row of occurrence index idx under ApplyMaps::valdiv
+__device__ __forceinline__ int bag_row(int idx, int valdiv) {
+    return static_cast<int>(static_cast<uint32_t>(idx) / static_cast<uint32_t>(valdiv));
+}
 enum : int { kPosMiss = 1, kPosInit = 2, kPosPush = 4, kPosHead = 8, kPosTemp = 16, kPosVictim = 32, kPosVictimHg = 64,
              kPosVictimPush = 128, kPosKeep = 256 };
 
@@ -513,6 +521,7 @@ __device__ __forceinline__ float chain_step(float acc, float m) {
 // (for its column quad).  Ends with the workgroup's partials consumed (a barrier precedes any reuse of s_part by the caller).
 // first / have_first: this wave's occurrence indices of the block at `lo`, fetched by the caller ahead of time (perm values, before
 // any valmap).
+template <bool BAGS = false>
 __device__ __forceinline__ float4v coop_tree_sum(const float *__restrict__ grads, const int32_t *__restrict__ perm,
                                                  const ApplyMaps &maps, int n, float lr, int s, int lo, int hi, int width,
                                                  int col, int w, float *s_part, int first = 0, bool have_first = false) {
@@ -533,6 +542,8 @@ __device__ __forceinline__ float4v coop_tree_sum(const float *__restrict__ grads
             p_next = perm[min(s + min(mine + 256 + (lane & 15), hi - 1), n - 1)];
         if (maps.valmap)
             pidx = maps.valmap[pidx];
+        if (BAGS && maps.valdiv)
+            pidx = bag_row(pidx, maps.valdiv);
         float4v g[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -568,7 +579,7 @@ __device__ __forceinline__ float4v coop_tree_sum(const float *__restrict__ grads
     return total;
 }
 
-template <int MODE>
+template <int MODE, bool BAGS = false>
 __device__ __forceinline__ void coop_slice_tree(float *__restrict__ dst_row, bool init, const float *__restrict__ grads,
                                                 const int32_t *__restrict__ perm, const ApplyMaps &maps, int n, float lr,
                                                 int s, int len, int width, int slice, int w, float *s_part, int first = 0,
@@ -581,7 +592,7 @@ __device__ __forceinline__ void coop_slice_tree(float *__restrict__ dst_row, boo
     float4v cur{0.f, 0.f, 0.f, 0.f};
     if (MODE != kModeReduce && init)
         cur = *reinterpret_cast<const float4v *>(dst_row + col);
-    const float4v total = coop_tree_sum(grads, perm, maps, n, lr, s, 0, len, width, col, w, s_part, first, have_first);
+    const float4v total = coop_tree_sum<BAGS>(grads, perm, maps, n, lr, s, 0, len, width, col, w, s_part, first, have_first);
     float4v nv;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -653,7 +664,7 @@ __device__ __forceinline__ void coop_chunk_tree(float *__restrict__ dst_row, boo
 
 // The worker part of a long run [s, s+len): this workgroup owns the 64-column slices j, j+workers, ...
 // All 16 waves call it (workgroup barriers inside); s_m = kCoopUnits x 64 floats of LDS.
-template <int MODE, int DUAL, int HAND = kHandNone>
+template <int MODE, int DUAL, int HAND = kHandNone, bool BAGS = false>
 __device__ __forceinline__ void coop_slices(
     float *__restrict__ dst_row, bool init, Second d2, const float *__restrict__ grads,
     const int32_t *__restrict__ perm, const ApplyMaps &maps, int n, float lr, int s, int len,
@@ -665,7 +676,7 @@ __device__ __forceinline__ void coop_slices(
     if (!DUAL && HAND == kHandNone && MODE != kModeOpt && maps.tree_from > 0 && len >= maps.tree_from &&
         (width & 3) == 0 && ((reinterpret_cast<uintptr_t>(dst_row) | reinterpret_cast<uintptr_t>(grads)) & 15) == 0) {
         for (int g0 = 0; g0 < my_slices; ++g0)   // every condition above is uniform over the workgroup
-            coop_slice_tree<MODE>(dst_row, init, grads, perm, maps, n, lr, s, len, width, j + g0 * workers, w, s_m);
+            coop_slice_tree<MODE, BAGS>(dst_row, init, grads, perm, maps, n, lr, s, len, width, j + g0 * workers, w, s_m);
         return;
     }
     // destinations of the key in the next batch, wave w takes w, w + 16, ...: looked up before the chain (two
@@ -717,6 +728,8 @@ __device__ __forceinline__ void coop_slices(
                 idx = perm[pos];
             if (maps.valmap)
                 idx = maps.valmap[idx];
+            if (BAGS && maps.valdiv)
+                idx = bag_row(idx, maps.valdiv);
             return idx;
         };
         auto request = [&](int idx) {
@@ -828,7 +841,7 @@ __device__ __forceinline__ void coop_slices(
 
 // Returns false when the run is shorter than kLongRun (the caller falls through to the per-wave
 // paths).  Called by all 16 waves of a full workgroup; wg0 = its first sorted position.
-template <int MODE, int DUAL, int HAND = kHandNone>
+template <int MODE, int DUAL, int HAND = kHandNone, bool BAGS = false>
 __device__ __forceinline__ bool coop_run(
     float *__restrict__ dst, uint64_t dst_rows, int width,
     const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
@@ -931,14 +944,14 @@ __device__ __forceinline__ bool coop_run(
     if (MODE == kModeOpt)
         opt_rows(d2, maps, row, width);
 
-    coop_slices<MODE, DUAL, HAND>(dst_row, init, d2, grads, perm, maps, n, lr, s, len, width, j, workers, w, s_m,
+    coop_slices<MODE, DUAL, HAND, BAGS>(dst_row, init, d2, grads, perm, maps, n, lr, s, len, width, j, workers, w, s_m,
                                  HAND == kHandSignal ? hd.pend + pend_slot(key) : nullptr, s_perm,
                                  wg0 - kCoopPermSpan, hd, key);
     return true;
 }
 
 // One wave per sorted position p; `lds` = kApplyLdsBytes of workgroup memory (long runs only).
-template <int MODE, int VEC, int DUAL, int HAND = kHandNone>
+template <int MODE, int VEC, int DUAL, int HAND = kHandNone, bool BAGS = false>
 __device__ __forceinline__ bool apply_body_impl(
     float *__restrict__ dst, uint64_t dst_rows, int width,
     const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
@@ -949,7 +962,7 @@ __device__ __forceinline__ bool apply_body_impl(
 // per position.  The early return below is taken by whole waves of the LAST workgroup only, which is
 // never a full one, so the barriers of coop_run see all 16 waves.
 // Returns true when the wave did medium / long-run work (false: it left early or applied a short run).
-template <int MODE, int VEC, int DUAL = false, int HAND = kHandNone>
+template <int MODE, int VEC, int DUAL = false, int HAND = kHandNone, bool BAGS = false>
 __device__ __forceinline__ bool apply_body(
     float *__restrict__ dst, uint64_t dst_rows, int width,
     const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
@@ -961,11 +974,11 @@ __device__ __forceinline__ bool apply_body(
     if (p >= n)
         return false;
     if (dbg == nullptr)
-        return apply_body_impl<MODE, VEC, DUAL, HAND>(dst, dst_rows, width, sorted, perm, upos, n, grads, lr, p, w, nullptr, maps, lds, hd);
+        return apply_body_impl<MODE, VEC, DUAL, HAND, BAGS>(dst, dst_rows, width, sorted, perm, upos, n, grads, lr, p, w, nullptr, maps, lds, hd);
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     const unsigned long long c0 = __builtin_amdgcn_s_memtime();
     int info = 0;
-    const bool heavy = apply_body_impl<MODE, VEC, DUAL, HAND>(dst, dst_rows, width, sorted, perm, upos, n, grads, lr, p, w, &info, maps, lds, hd);
+    const bool heavy = apply_body_impl<MODE, VEC, DUAL, HAND, BAGS>(dst, dst_rows, width, sorted, perm, upos, n, grads, lr, p, w, &info, maps, lds, hd);
     __builtin_amdgcn_s_waitcnt(0);
     const unsigned long long c1 = __builtin_amdgcn_s_memtime();
     const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
@@ -978,7 +991,7 @@ __device__ __forceinline__ bool apply_body(
     return heavy;
 }
 
-template <int MODE, int VEC, int DUAL, int HAND>
+template <int MODE, int VEC, int DUAL, int HAND, bool BAGS>
 __device__ __forceinline__ bool apply_body_impl(
     float *__restrict__ dst, uint64_t dst_rows, int width,
     const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
@@ -1007,6 +1020,8 @@ __device__ __forceinline__ bool apply_body_impl(
         pit = maps.pos_item[p];
     if (maps.valmap)  // wave-uniform
         pv = maps.valmap[pv];
+    if (BAGS && maps.valdiv)
+        pv = bag_row(pv, maps.valdiv);
     const uint32_t key = static_cast<uint32_t>(
         __builtin_amdgcn_readlane(static_cast<int>(ks), kLookBack));
     // a FULL workgroup: its 16 positions hold one key (every wave of it reaches the same verdict)
@@ -1017,7 +1032,7 @@ __device__ __forceinline__ bool apply_body_impl(
             return false;   // >= nslice full workgroups of this run precede: not a worker
         if (dbg_info)
             *dbg_info = (w << 16) | 0x7FFF;
-        if (coop_run<MODE, DUAL, HAND>(dst, dst_rows, width, sorted, perm, upos, n, grads, lr, wg0, w, key, bk, fk, maps, lds, hd, spv))
+        if (coop_run<MODE, DUAL, HAND, BAGS>(dst, dst_rows, width, sorted, perm, upos, n, grads, lr, wg0, w, key, bk, fk, maps, lds, hd, spv))
             return true;
     }
     const unsigned long long eq = __ballot(q >= 0 && q < n && ks == key);

@@ -3,6 +3,8 @@ when, and on which buffers -- without the graph executor around them.
 
 Mirrors (paths relative to /root/reference):
   EmbeddingLookUp / EmbeddingLookUp_Gradient      python/hetu/gpu_ops/EmbeddingLookUp.py:10-125
+  EmbeddingLookUpSum / EmbeddingLookUpSum_Gradient  the same followed by reduce_sum_op(axes=1), python/hetu/gpu_ops/ReduceSum.py
+                                                  (examples/ctr/models/emb_sum_*.py)
   ParameterServerCommunicateOp                    python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
   ParameterServerSparsePullOp                     python/hetu/gpu_ops/ParameterServerCommunicate.py:254-306
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
@@ -114,9 +116,70 @@ class EmbeddingLookUp_Gradient:
         return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape)
 
 
+class EmbeddingLookUpSum(EmbeddingLookUp):
+    """embedding_lookup_op(embedding, index) followed by reduce_sum_op(axes=1), the pair of the reference's pooled CTR models
+    (examples/ctr/models/emb_sum_wdl_criteo.py:14-16): compute(ids[B, F], output_val[B, width]) -- or ids[n] with
+    offsets[B + 1] for ragged bags.  With a device table it is the fused kernel (ops.embedding_lookup_sum).  On the PS, cache
+    and prefetched paths the per-occurrence rows arrive as EmbeddingLookUp delivers them and the same kernel sums them, in the
+    same position order, out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Those paths are
+    not fused: they still move [n, width] rows."""
+
+    def forward_hook(self, config):
+        super().forward_hook(config)
+        self._rows_compute = self.compute
+        self._fused = self._rows_compute == self._compute_gpu
+        self._pos = None
+        self.compute = self._compute_sum
+
+    def _compute_sum(self, ids, output_val, stream=None, offsets=None):
+        if self._fused:
+            return ops.embedding_lookup_sum(self.embedding.table, ids, offsets=offsets, out=output_val, stream=stream)
+        n, width = ids.numel(), self.embedding.shape[1]
+        if self._pos is None or self._pos.numel() < n or self._pos.device != output_val.device:
+            self._pos = torch.arange(max(n, 1), dtype=torch.int64, device=output_val.device)
+        # (a buffer per call, as the per-occurrence operator's caller allocates its output: the cache fills it on its own stream)
+        rows = torch.empty((n, width), dtype=torch.float32, device=output_val.device)
+        self._rows_compute(ids, rows.view(tuple(ids.shape) + (width,)), stream)
+        return ops.embedding_lookup_sum(rows, self._pos[:n].view(ids.shape), offsets=offsets, out=output_val, stream=stream)
+
+
+class EmbeddingLookUpSum_Gradient:
+    """The gradient of the pair: reduce_sum's gradient broadcasts the pooled gradient row to the bag's occurrences, and
+    EmbeddingLookUp_Gradient wraps it as IndexedSlices.  Here the broadcast is not materialised: compute(vectors[B, width],
+    index) returns POOLED IndexedSlices (values stay [B, width])."""
+
+    def __init__(self, embed_shape, enable_push_index=False):
+        self.embed_shape, self.enable_push_index = embed_shape, enable_push_index
+
+    def compute(self, vectors, index, offsets=None):
+        push = None
+        if isinstance(index, tuple):
+            index, push = index[0], (index[1] if self.enable_push_index else None)
+        elif self.enable_push_index:
+            raise TypeError
+        if offsets is None:
+            if index.dim() != 2:
+                raise ValueError("fixed bags need an index of shape [B, F]; give offsets for ragged bags")
+            return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
+                                     bag=index.shape[1])
+        return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
+                                 bag_of=ops.bag_of(offsets, index.numel()))
+
+
 def sgd_update_sparse(param, grad, lr, stream=None):
     """OptimizerOp's sparse SGD branch on a device table (OptimizerLink.py:23-33): no dedup, duplicates in
-    occurrence order."""
+    occurrence order.  Pooled slices (EmbeddingLookUpSum_Gradient) go to the bag apply: no expanded gradient is built."""
+    if getattr(grad, "pooled", False):
+        width = param.table.shape[1]
+        values = grad.values.reshape(-1, width).contiguous()
+        if grad.bag is not None:
+            ops.sgd_sparse_update_bags(param.table, grad.indices.reshape(-1, int(grad.bag)).contiguous(), values, lr,
+                                       stream=stream)
+        else:
+            ids = grad.indices.reshape(-1).contiguous()
+            plan = ops.IndexPlan(max(ids.numel(), 1), device=ids.device).sort(ids, stream)
+            ops.sgd_apply_bags(param.table, plan, values, lr, bag_of=grad.bag_of, stream=stream)
+        return
     ops.dl_call("SGDOptimizerSparseUpdate",
                 [param.table, grad.indices.contiguous(), grad.values.reshape(-1, param.table.shape[1]).contiguous()],
                 scalars=[ctypes.c_float(lr)], stream=stream)
@@ -204,10 +267,21 @@ class ParameterServerCommunicateOp:
             self._peek_offset = 1
 
     # -- compute variants (:37-56)
+    @staticmethod
+    def _per_occurrence(grad):
+        """Pooled slices (the gradient of EmbeddingLookUpSum: one row per bag) are expanded to per-occurrence values before
+        they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The PS, cache and
+        step-engine paths are NOT fused for pooled access: they move the expanded [n, width] values as they always did."""
+        if not getattr(grad, "pooled", False):
+            return grad
+        return ops.IndexedSlices(indices=grad.indices, values=grad.expanded_values(), dense_shape=grad.dense_shape,
+                                 push_indices=grad.push_indices)
+
     def _mult_lr(self, grad):
         scale_(grad.values, self.learning_rate)
 
     def _compute_asp_prefetch(self, grad):
+        grad = self._per_occurrence(grad)
         self._mult_lr(grad)
         self.config.ps_map[self.parameter] = (self._push_pull(grad), self.sparse_pull_val)
 
@@ -216,6 +290,7 @@ class ParameterServerCommunicateOp:
         (ps-lite/include/ps/server/ssp_handler.h:41-67).  The sparse push / pull of a sharded store are
         collectives over all ranks, so no rank can run ahead at all: every tolerance is served by the
         lock step of the exchange itself, which satisfies the bound; only the version counter is kept."""
+        grad = self._per_occurrence(grad)
         self._mult_lr(grad)
         w = self._push(grad)
         if w is not None:
@@ -225,6 +300,7 @@ class ParameterServerCommunicateOp:
         self.ssp_version += 1
 
     def _compute_bsp_prefetch(self, grad):
+        grad = self._per_occurrence(grad)
         self._mult_lr(grad)
         w = self._push(grad)
         if w is not None:
@@ -233,6 +309,7 @@ class ParameterServerCommunicateOp:
         self.config.ps_map[self.parameter] = (self._pull(self.next_ids()), self.sparse_pull_val)
 
     def _compute_no_prefetch(self, grad):
+        grad = self._per_occurrence(grad)
         self._mult_lr(grad)
         w = self._push(grad)
         if w is not None:

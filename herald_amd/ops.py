@@ -306,6 +306,100 @@ def sgd_sparse_update(table, ids, grads, lr, stream=None):
     return table
 
 
+# ---- sum-pooled lookup (bags) ------------------------------------------------------------------------
+def _ids_fn(ids, f32, u64):
+    if ids.dtype == torch.float32:
+        return f32
+    if ids.dtype in (torch.int64, torch.uint64):
+        return u64
+    raise TypeError("ids must be float32 or (u)int64")
+
+
+def _bag_shape(ids, offsets):
+    """(n, bag, nbags) of a bag layout: fixed bags ids[B, F] (offsets None), or ragged ids[n] with offsets[B + 1]."""
+    if not ids.is_cuda or not ids.is_contiguous():
+        raise ValueError("ids must be a contiguous device tensor")
+    n = ids.numel()
+    if offsets is None:
+        if ids.dim() != 2:
+            raise ValueError("fixed bags need ids of shape [B, F]; give offsets for ragged bags")
+        if ids.shape[1] < 1:
+            raise ValueError("fixed bags need at least one id per bag")
+        return n, ids.shape[1], ids.shape[0]
+    _require(offsets, torch.int64, "offsets")
+    if ids.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("ragged bags need ids of shape [n] and offsets of shape [B + 1]")
+    return n, 0, offsets.numel() - 1
+
+
+def embedding_lookup_sum(table, ids, offsets=None, out=None, stream=None):
+    """Sum-pooled lookup: out[b, :] = ((0 + r_0) + r_1) + ... over the table rows of bag b's ids, in position order (one
+    rounding per term; an id >= rows adds a zero row, an empty bag gives zeros).  ids [B, F] (fixed bags) or ids [n] with
+    offsets int64 [B + 1] (ragged bags, offsets[0] = 0, offsets[B] = n, non-decreasing).  Returns out [B, width]."""
+    L = _lib.load()
+    _require(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    width = table.shape[1]
+    if out is None:
+        out = torch.empty((nbags, width), dtype=torch.float32, device=table.device)
+    _require(out, torch.float32, "out")
+    if out.numel() != nbags * width:
+        raise ValueError("out has the wrong size")
+    fn = _ids_fn(ids, L.ha_gather_sum_f32ids, L.ha_gather_sum_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), n, bag, _ptr(offsets) if offsets is not None else None, nbags,
+             _ptr(out), _stream_ptr(stream)), "ha_gather_sum")
+    return out
+
+
+def bag_of(offsets, n, out=None, stream=None):
+    """int32 [n]: the bag of every occurrence of ragged bags (what sgd_apply_bags takes)."""
+    _require(offsets, torch.int64, "offsets")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=offsets.device)
+    _require(out, torch.int32, "out")
+    if out.numel() != n:
+        raise ValueError("out has the wrong size")
+    check(_lib.load().ha_bag_of(_ptr(offsets), offsets.numel() - 1, n, _ptr(out), _stream_ptr(stream)), "ha_bag_of")
+    return out
+
+
+def sgd_apply_bags(table, plan, bag_grads, lr, bag=None, bag_of=None, stream=None):
+    """table[key_i, :] -= lr * bag_grads[bag of i, :] for every occurrence i of the planned ids, in occurrence order: the
+    sparse SGD apply of a sum-pooled lookup, bit for bit sgd_apply on bag_grads.repeat_interleave.  Give `bag` (fixed bags
+    of that many ids) or `bag_of` (int32 [n], from ops.bag_of).  The plan needs to be sorted only."""
+    _require(table, torch.float32, "table")
+    _require(bag_grads, torch.float32, "bag_grads")
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != plan.n:
+            raise ValueError("bag_of must have one entry per planned id")
+    elif bag < 1 or plan.n % bag or bag_grads.numel() != (plan.n // bag) * table.shape[1]:
+        raise ValueError("bag_grads must be [n / bag, width]")
+    check(_lib.load().ha_sgd_apply_bags(_ptr(table), table.shape[0], table.shape[1], _ptr(plan.ws), plan.n, _ptr(bag_grads),
+                                        int(bag) if bag is not None else 0, _ptr(bag_of) if bag_of is not None else None,
+                                        ctypes.c_float(lr), _stream_ptr(stream)), "ha_sgd_apply_bags")
+    return table
+
+
+def sgd_sparse_update_bags(table, ids, bag_grads, lr, offsets=None, stream=None):
+    """One call: plan + sgd_apply_bags.  ids / offsets as in embedding_lookup_sum, bag_grads [B, width]."""
+    L = _lib.load()
+    _require(table, torch.float32, "table")
+    _require(bag_grads, torch.float32, "bag_grads")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    if bag_grads.numel() != nbags * table.shape[1]:
+        raise ValueError("bag_grads must be [B, width]")
+    fn = _ids_fn(ids, L.ha_sgd_sparse_update_bags_f32ids, L.ha_sgd_sparse_update_bags_u64ids)
+    check(fn(_ptr(table), table.shape[0], table.shape[1], _ptr(ids), n, _ptr(bag_grads), bag,
+             _ptr(offsets) if offsets is not None else None, nbags, ctypes.c_float(lr), _stream_ptr(stream)),
+          "ha_sgd_sparse_update_bags")
+    return table
+
+
 # ---- fused launches: two per training step --------------------------------------------------------
 def lookup_sort(table, ids, plan, out=None, stream=None):
     """Forward of one batch in ONE launch: out = table[ids] and plan.sort(ids)."""
@@ -1324,12 +1418,35 @@ class IndexedSlices:
     exactly what the reference computes with np.unique + DeduplicateIndexedSlices / cpu_deduplicate.
     """
 
-    def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None):
+    def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None):
+        """bag / bag_of (optional): POOLED slices, the gradient of a sum-pooled lookup -- values is [B, width], one row per
+        bag, and occurrence i of indices takes the row of its bag: i // bag (fixed bags of `bag` ids) or bag_of[i] (int32 [n],
+        ragged bags)."""
+        if bag is not None and bag_of is not None:
+            raise ValueError("give at most one of bag and bag_of")
         self.indices = indices
         self.values = values
         self.dense_shape = dense_shape
         self.push_indices = push_indices
+        self.bag, self.bag_of = bag, bag_of
         self.deduplicated = False
+
+    @property
+    def pooled(self):
+        return self.bag is not None or self.bag_of is not None
+
+    def expanded_values(self, stream=None):
+        """Per-occurrence values [n, width] of pooled slices (every occurrence a copy of its bag's row)."""
+        width = self.values.shape[-1]
+        vals = self.values.reshape(-1, width).contiguous()
+        if not self.pooled:
+            return vals
+        n = self.indices.numel()
+        if self.bag is not None:
+            rows = torch.arange(n, dtype=torch.int64, device=vals.device) // int(self.bag)
+        else:
+            rows = self.bag_of.reshape(-1).to(torch.int64)
+        return embedding_lookup(vals, rows, stream=stream)      # (the gather kernel: occurrence i <- row of its bag)
 
     def get_dense_shape(self):
         assert self.dense_shape is not None
@@ -1338,9 +1455,10 @@ class IndexedSlices:
     def get_sparse_shape(self):
         return tuple(self.values.shape)
 
-    def update(self, indices, values, dense_shape, push_indices=None):
+    def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None):
         self.indices = indices
         self.push_indices = push_indices
+        self.bag, self.bag_of = bag, bag_of
         self.values = values
         if self.dense_shape is not None:
             assert tuple(self.dense_shape) == tuple(dense_shape)
@@ -1349,6 +1467,8 @@ class IndexedSlices:
         self.deduplicated = False
 
     def deduplicate(self, stream=None):
+        if self.pooled:
+            raise ValueError("pooled IndexedSlices (bag / bag_of) cannot be deduplicated: values holds one row per bag")
         ids = self.indices.reshape(-1)
         n = ids.numel()
         width = self.values.shape[-1]
@@ -1366,6 +1486,8 @@ class IndexedSlices:
         return self
 
     def to_dense(self, stream=None):
+        if self.pooled:
+            raise ValueError("pooled IndexedSlices (bag / bag_of) have no dense form: values holds one row per bag")
         dense = torch.zeros(tuple(self.get_dense_shape()), dtype=torch.float32, device=self.values.device)
         dl_call("IndexedSlices2Dense", [self.values.contiguous(), self.indices.contiguous(), dense],
                 stream=stream)

@@ -1178,6 +1178,45 @@ int ha_sgd_sparse_update_f32ids(float *table, int64_t rows, int64_t width,
                                 const float *grads, float lr,
                                 ha_stream_t stream);
 
+/* ---- sum-pooled embedding lookup ("bags") and its sparse SGD apply ------------------------------------
+ * The fused form of embedding_lookup_op + reduce_sum_op(axes=1) of the reference's pooled CTR models
+ * (examples/ctr/models/emb_sum_*.py).  A BAG is the list of ids of one sample.
+ *   fixed bags : bag >= 1, offsets NULL -- ids is [nbags, bag] (n == nbags * bag), occurrence i is in bag i / bag;
+ *   ragged bags: bag == 0, offsets = device int64[nbags + 1], offsets[0] = 0, offsets[nbags] = n, non-decreasing --
+ *                bag b is ids[offsets[b] : offsets[b + 1]]; empty bags are allowed.
+ * Exactly one of the two is given.  The kernels clamp every offset to [0, n]: no id at or beyond n is read and no
+ * output row at or beyond nbags written, whatever offsets holds.
+ *
+ * Forward: out[b,:] = ((0.0f + r_0) + r_1) + ... + r_{m-1}, r_j = the table row of the bag's j-th id, added in position
+ * order with one rounding per term (the reference's own order is unspecified; this one is the same on every path here).
+ * An id >= rows contributes a zero row, as in ha_gather_*; an empty bag gives zeros.  Any width >= 1; width % 4 == 0
+ * with 16-byte aligned table / out takes the 16-byte path. */
+int ha_gather_sum_f32ids(const float *table, int64_t rows, int64_t width, const float *ids, int64_t n, int64_t bag,
+                         const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
+int ha_gather_sum_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
+                         const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
+/* bag_of[i] (int32[n]) = the bag of occurrence i of ragged bags; always in [0, nbags). */
+int ha_bag_of(const int64_t *offsets, int64_t nbags, int64_t n, int32_t *bag_of, ha_stream_t stream);
+/* Backward: bag_grads is the gradient of the pooled output, [nbags, width]; occurrence i takes the row of its bag:
+ *   table[key_i,:] -= lr * bag_grads[bag_of(i),:]   for every occurrence, in occurrence order, two roundings each
+ * -- bit for bit what ha_sgd_apply gives on bag_grads expanded to [n, width] (cpu_SGDOptimizerSparseUpdate on
+ * reduce_sum's broadcast gradient) and what ha_apply_mapped gives with valmap = bag_of, in tolerance mode too.
+ * plan_ws: a plan of the n ids, sorted (ha_plan_sort_*) or finished.  Fixed bags: bag >= 1, bag_of NULL -- the source
+ * row i / bag is computed in registers; ragged bags: bag == 0 and bag_of from ha_bag_of (every entry must name a row of
+ * bag_grads).  One wave per sorted position for every n. */
+int ha_sgd_apply_bags(float *table, int64_t rows, int64_t width, const void *plan_ws, int64_t n, const float *bag_grads,
+                      int64_t bag, const int32_t *bag_of, float lr, ha_stream_t stream);
+/* One call: plan + (ha_bag_of +) ha_sgd_apply_bags, on an internal per-stream workspace. */
+int ha_sgd_sparse_update_bags_f32ids(float *table, int64_t rows, int64_t width, const float *ids, int64_t n,
+                                     const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags, float lr,
+                                     ha_stream_t stream);
+int ha_sgd_sparse_update_bags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n,
+                                     const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags, float lr,
+                                     ha_stream_t stream);
+/* Measurement aid (tools/bag_bench.py): column-slice width of ha_gather_sum_*'s 16-byte path, 64 / 128 / 256 floats per
+ * wave; 0 = chosen from the batch (the default).  Process-wide; results do not depend on it. */
+int ha_debug_bag_slice(int floats);
+
 /* ---- in-node parameter-server engine behind the libps names (include/herald_ps.h) --------------------
  * ps-lite/src/python_binding.cc:6-151 -> Worker -> PSAgent (PSAgent.h:124-237) -> servers
  * (PSFHandle.h:101-164, 401-439).  Every process owns the AveragePartitioner row range of its rank
