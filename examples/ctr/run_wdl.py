@@ -36,7 +36,9 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      before the tower (embedding_lookup_op + reduce_sum_op(axes=1)).  --embedding hbm: the fused sum-pooled
                      lookup (ha_gather_sum_*) and the bag apply (ha_sgd_apply_bags) -- neither [B, 26, d] nor the expanded
                      gradient is built; ps / cache: per-occurrence rows as before, summed in the same order, the pooled
-                     gradient expanded before the push.  The step engines refuse the model.
+                     gradient expanded before the push -- except --embedding cache --cache-planned --bsp 0, where the
+                     cache's planned pairs are pooled as well (ha_cache_lookup_sum_planned /
+                     ha_cache_update_planned_bags).  The step engines refuse the model.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -238,12 +240,15 @@ def make_batches(nbatch, batch, rows, seed=0, rank=0, world=1):
 
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
-          bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False):
+          bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
     planned lookup + update pairs; at bsp < 0 (asp, the command line's default) with the LRU policy the planned push-pull chain:
     one cache call per training step, which needs cache_limit >= 2 * batch * 26 (the default limit takes that into account).
+    A pooled model (emb_sum_wdl) on the planned pairs (bsp 0) pulls and pushes POOLED rows: the communicate op is told the bag
+    size, the cache sums a sample's 26 rows as it reads them and takes the [batch, width] gradient as it is
+    (cache_fuse_bags=False: the unfused path, the same bits).
     The ring wraps round, so the chain is still open when training ends, with one step's bookkeeping planned ahead and never
     run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
     replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests)."""
@@ -283,9 +288,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                  cstable_policy=cache if embedding == "cache" else None, cache_bound=bound,
                                  cache_limit=cache_limit if cache_limit is not None else
                                  max(rows // 10, batch * NFIELD * (2 if cache_planned and bsp < 0 else 1)),
-                                 cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned)
+                                 cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned, cache_fuse_bags=cache_fuse_bags)
         comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: ids_of(state["k"] + 1),
-                                                     peek_ids=lambda j: ids_of(state["k"] + 1 + j))
+                                                     peek_ids=lambda j: ids_of(state["k"] + 1 + j),
+                                                     bag=NFIELD if pooled and embedding == "cache" else None)
         barrier = dist.barrier if world > 1 else (lambda: None)
         comm.forward_hook(config, first_ids=ids_of(0), barrier=barrier)
     if pooled:
@@ -419,6 +425,8 @@ def main():
                     help="--embedding cache, or --laia: the cache's planned flow (bookkeeping of the next batch beside "
                          "this step; --bsp 0: planned lookup + update pairs; --bsp -1, the default, with --cache lru: the planned "
                          "push-pull chain, one cache call per step, cache limit >= 2 * batch * 26; "
+                         "--model emb_sum_wdl at --bsp 0: the pairs are pooled -- the cache sums a sample's 26 rows as it "
+                         "reads them and takes the [batch, width] gradient as it is, no [batch * 26, width] tensor; "
                          "--laia: the update pushes the batch's push plan).  With --laia at world size > 1 it is "
                          "accepted and has no effect (the cache there talks to a remote store, call by call)")
     ap.add_argument("--nepoch", type=int, default=-1, help="epochs of `--steps` steps each (default: one)")

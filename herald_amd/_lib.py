@@ -277,6 +277,9 @@ def _declare(L):
         "ha_cache_update_planned": [vp, i64, vp, vp],
         "ha_cache_plan_pending": [vp],
         "ha_cache_run_planned_pairs": [vp, c.c_int, vp, vp, vp, vp],
+        "ha_cache_lookup_sum_planned": [vp, i64, i64, i64, vp, vp, vp],
+        "ha_cache_update_planned_bags": [vp, i64, vp, i64, i64, vp, vp],
+        "ha_cache_run_planned_pairs_bags": [vp, c.c_int, i64, i64, i64, vp, vp, vp],
         "ha_cache_plan_block_push_pull": [vp, vp, c.c_int, vp, c.c_int, vp, vp],
         "ha_cache_push_pull_planned": [vp, i64, vp, i64, vp, vp],
         "ha_cache_run_planned_push_pulls": [vp, c.c_int, vp, vp, vp, vp, vp],

@@ -664,6 +664,98 @@ class _CacheBase:
               "ha_cache_run_planned_pairs")
         del pl[:cnt]
 
+    # ---- sum-pooled access in the planned flow (csrc/cache_block.hip): the [n, width] rows / gradients are never materialised
+    def _pooled_due(self, who, lookup):
+        if getattr(self, "_chain", None) or getattr(self, "_chain_last", None) is not None:
+            raise ValueError("%s: a planned push-pull chain is open: its steps are not pooled" % who)
+        pl = getattr(self, "_planned", None)
+        if not pl or pl[0][1] == lookup:
+            raise ValueError("%s: %s" % (who, "no planned batch is due for its lookup" if lookup else
+                                         "the lookup of the planned batch comes first"))
+        return pl[0][0]
+
+    def _pooled_args(self, who, what, x, n, bag, ragged, ragged_name):
+        """Checks of a pooled call, before anything native: x float32 contiguous device [nbags, width]; exactly one of `bag`
+        (fixed bags: nbags * bag == n) and the ragged description (offsets: int64 [nbags + 1]; bag_of: int32 [n]).  -> nbags"""
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2 and
+                x.shape[1] == self._width):
+            raise ValueError("%s: %s must be a contiguous float32 device tensor [nbags, %d]" % (who, what, self._width))
+        nbags = int(x.shape[0])
+        if (bag is None) == (ragged is None):
+            raise ValueError("%s: give exactly one of bag and %s" % (who, ragged_name))
+        if bag is not None:
+            bag = int(bag)
+            if bag < 1 or nbags * bag != n:
+                raise ValueError("%s: %d bags of %d ids are not the planned batch's %d ids" % (who, nbags, bag, n))
+            return nbags
+        want_dtype, want_len = (torch.int64, nbags + 1) if ragged_name == "offsets" else (torch.int32, n)
+        if not (torch.is_tensor(ragged) and ragged.is_cuda and ragged.dtype == want_dtype and ragged.is_contiguous() and
+                ragged.dim() == 1 and ragged.numel() == want_len):
+            raise ValueError("%s: %s must be a contiguous %s device tensor [%d]" % (who, ragged_name, want_dtype, want_len))
+        if n > 0 and nbags < 1:
+            raise ValueError("%s: %d ids in no bag" % (who, n))
+        return nbags
+
+    def embedding_lookup_sum_planned(self, out, bag=None, offsets=None):
+        """The lookup of the next planned batch, delivered SUM-POOLED (ha_cache_lookup_sum_planned), ONE launch: out[b,:] =
+        ((0 + r_lo) + r_lo+1) + ... over the rows of bag b's ids in position order -- bit for bit embedding_lookup_planned
+        followed by ops.embedding_lookup_sum over the rows; the cache is left as that lookup leaves it.  out: float32 device
+        tensor [nbags, width]; bag: fixed bags of `bag` ids (nbags * bag == n), or offsets: int64 device tensor [nbags + 1]
+        (offsets[0] = 0, offsets[nbags] = n, non-decreasing; clamped to [0, n])."""
+        who = "embedding_lookup_sum_planned"
+        k = self._pooled_due(who, True)
+        nbags = self._pooled_args(who, "out", out, k.numel(), bag, offsets, "offsets")
+        s = self._stream()
+        check(self._L.ha_cache_lookup_sum_planned(self._h, k.numel(), nbags, int(bag) if bag is not None else 0,
+                                                  ctypes.c_void_p(offsets.data_ptr() if offsets is not None else None),
+                                                  ctypes.c_void_p(out.data_ptr() if nbags else None),
+                                                  ctypes.c_void_p(s.cuda_stream)), "ha_cache_lookup_sum_planned")
+        self._planned[0][1] = True
+        if self.perf_enabled:
+            self._perf_record(0)
+        return Wait(s, [k, out, offsets]) if self._planned_waits else None
+
+    def embedding_update_planned_bags(self, bag_grads, bag=None, bag_of=None):
+        """The update of the planned batch whose lookup was the last planned call, from the POOLED gradient bag_grads [nbags,
+        width] (ha_cache_update_planned_bags), ONE launch: bit for bit embedding_update_planned(bag_grads[bag of every id]).
+        bag: fixed bags of `bag` ids, or bag_of: int32 device tensor [n], the bag of every id (ops.bag_of(offsets, n))."""
+        who = "embedding_update_planned_bags"
+        k = self._pooled_due(who, False)
+        nbags = self._pooled_args(who, "bag_grads", bag_grads, k.numel(), bag, bag_of, "bag_of")
+        s = self._stream()
+        check(self._L.ha_cache_update_planned_bags(self._h, k.numel(), ctypes.c_void_p(bag_grads.data_ptr() if nbags else None),
+                                                   nbags, int(bag) if bag is not None else 0,
+                                                   ctypes.c_void_p(bag_of.data_ptr() if bag_of is not None else None),
+                                                   ctypes.c_void_p(s.cuda_stream)), "ha_cache_update_planned_bags")
+        self._planned.pop(0)
+        if self.perf_enabled:
+            self._perf_record(1)
+        return Wait(s, [k, bag_grads, bag_of]) if self._planned_waits else None
+
+    def run_planned_pairs_bags(self, outs, bag_grads, bag):
+        """The next len(outs) planned pairs by ONE library call (ha_cache_run_planned_pairs_bags), pooled both ways with fixed
+        bags of `bag` ids: lookup into outs[k] [nbags, width], update with bag_grads[k] [nbags, width].  Every pair has the same
+        number of ids.  For callers that have the pairs' gradient buffers at hand (a benchmark loop); no perf records."""
+        who = "run_planned_pairs_bags"
+        cnt = len(outs)
+        pl = getattr(self, "_planned", None) or []
+        if getattr(self, "_chain", None) or cnt > len(pl) or len(bag_grads) != cnt or (pl and pl[0][1]):
+            raise ValueError("%s: %d pairs, %d planned" % (who, cnt, len(pl)))
+        if cnt == 0:
+            return
+        n = pl[0][0].numel()
+        if any(pl[k][0].numel() != n for k in range(cnt)):
+            raise ValueError("%s: the pairs of one call have the same number of ids" % who)
+        nbags = {self._pooled_args(who, "outs[%d]" % k, outs[k], n, bag, None, "offsets") for k in range(cnt)} | \
+                {self._pooled_args(who, "bag_grads[%d]" % k, bag_grads[k], n, bag, None, "bag_of") for k in range(cnt)}
+        nbags = nbags.pop()
+        s = self._stream()
+        op = (ctypes.c_void_p * cnt)(*[o.data_ptr() if nbags else None for o in outs])
+        gp = (ctypes.c_void_p * cnt)(*[g.data_ptr() if nbags else None for g in bag_grads])
+        check(self._L.ha_cache_run_planned_pairs_bags(self._h, cnt, n, nbags, int(bag), op, gp, ctypes.c_void_p(s.cuda_stream)),
+              "ha_cache_run_planned_pairs_bags")
+        del pl[:cnt]
+
     _planned_waits = True      # False: the planned calls return None instead of a wait handle (no event per call: bench loops)
 
     def embedding_lookup(self, keys, dest):
@@ -983,6 +1075,17 @@ class CacheSparseTable:
 
     def run_planned_pairs(self, dests, grads):
         self.cache.run_planned_pairs(dests, grads)
+
+    def embedding_lookup_sum_planned(self, out, bag=None, offsets=None, sync=False):
+        w = self.cache.embedding_lookup_sum_planned(out, bag=bag, offsets=offsets)
+        return self._finish(w, sync) if w is not None else None
+
+    def embedding_update_planned_bags(self, bag_grads, bag=None, bag_of=None, sync=False):
+        w = self.cache.embedding_update_planned_bags(bag_grads, bag=bag, bag_of=bag_of)
+        return self._finish(w, sync) if w is not None else None
+
+    def run_planned_pairs_bags(self, outs, bag_grads, bag):
+        self.cache.run_planned_pairs_bags(outs, bag_grads, bag)
 
     def looked_up_last(self, keys):
         """True when `keys` is the device tensor the cache's last operation, an embedding_lookup, was given (same storage,

@@ -1094,6 +1094,184 @@ __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
         pver[p] = sv + adj;
 }
 
+// ---- the lookup of a planned batch, delivered SUM-POOLED: ONE launch, a wave per (bag, column slice) ------------------------
+// out[b,:] = ((0.0f + r_lo) + r_lo+1) + ... over the rows r_j that cache_lookup_planned_kernel would have written for the
+// occurrences j of bag b, in position order, one __fadd_rn per term (bagsum.hip's chain: what ha_cache_lookup_planned followed
+// by ha_gather_sum over the ids 0 .. n-1 gives, bit for bit); the [n, width] rows are never written.  The mapping is
+// bag_sum_kernel's: a bag is split over waves by COLUMNS only, lane l of a block of 64 positions fetches what its occurrence
+// needs, the row pointers are broadcast with v_readlane and ROWS clamped row loads are in flight before the first add.
+//
+// What an occurrence needs is reached through the batch's index plan instead of a record per sorted position: the item of
+// occurrence i is {it_slot, uniq, it_flag}[inverse[i]], the key's head occurrence (the FIRST one, the sort is stable) is
+// perm[seg[u]] and its staged version lies at pver[seg[u]] -- where the update's meta role, which walks the sorted positions,
+// looks for it.  Three dependent round trips per block of 64 positions: inverse; the item and seg; the two versions and perm.
+//
+// One writer.  Every wave that meets key u takes the pull decision from srv_ver[key] and line[slot].version, words nothing in
+// this launch writes (see cache_lookup_planned_kernel), so all of them agree.  A line that is not pulled is read from its data
+// row, which nobody writes.  A pulled key is read by EVERY wave from the store (+ the line's gradient row, Line::addup), never
+// from the data row being refreshed; the waves whose bag holds the key's head occurrence store the refreshed row there, each
+// its own column slice, and the slice-0 wave of them stages the version.  (Bags of a batch are disjoint ranges of positions,
+// so that is one wave per slice.)
+// An item no bookkeeping launch wrote: sticky word 3 as in cache_lookup_planned_kernel, a zero row, nothing refreshed.
+template <int VEC>
+struct SumVec;
+template <>
+struct SumVec<1> {
+    typedef float T;
+    static __device__ __forceinline__ float get(const T &v, int) { return v; }
+    static __device__ __forceinline__ void set(T &v, int, float x) { v = x; }
+};
+template <>
+struct SumVec<2> {
+    typedef float T __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
+    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
+};
+template <>
+struct SumVec<4> {
+    typedef float4v T;
+    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
+    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
+};
+struct SumPlan {
+    const int32_t *it_slot;      // per unique key of the batch (BookArgs)
+    const uint8_t *it_flag;
+    const uint32_t *uniq;
+    const int32_t *inverse;      // [n] unique index of occurrence i
+    const int32_t *seg;          // [U] first sorted position of unique key u
+    const int32_t *perm;         // [n] occurrence index of sorted position p
+    long long *pver;             // [n] staged versions, per sorted position (the heads')
+    const PlanRec *rec;
+};
+constexpr int kSumWaves = 4;     // waves per workgroup
+// row-pointer flags of a lane's occurrence
+constexpr int kSumOk = 1, kSumGrad = 2, kSumHead = 4;
+
+template <int VEC, int ROWS>
+__global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_kernel(
+    Cache c, SumPlan sp, long long n, long long bag, const int64_t *__restrict__ offsets, long long nbags, uint32_t nslice,
+    float *__restrict__ out) {
+    typedef typename SumVec<VEC>::T V;
+    typedef const V __attribute__((address_space(1))) *GlobalV;
+    const int lane = lane_id();
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kSumWaves + (threadIdx.x >> 6);   // wave-uniform
+    if (item >= static_cast<uint64_t>(nbags) * nslice)
+        return;
+    const long long b = static_cast<long long>(item / nslice);
+    const uint32_t sl = static_cast<uint32_t>(item - static_cast<uint64_t>(b) * nslice);
+    long long lo, hi;
+    if (offsets != nullptr) {
+        lo = offsets[b];
+        hi = offsets[b + 1];
+        lo = lo < 0 ? 0 : (lo > n ? n : lo);
+        hi = hi < lo ? lo : (hi > n ? n : hi);
+    } else {
+        lo = b * bag;
+        hi = lo + bag;      // (n == nbags * bag: checked by the host)
+    }
+    const uint32_t width = static_cast<uint32_t>(c.width);
+    const uint32_t col = (sl * kWave + lane) * VEC;
+    const bool live = col < width;       // (VEC > 1: width % VEC == 0, so a live lane's VEC columns all exist)
+    const uint32_t lcol = live ? col : 0;
+    V acc;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+        SumVec<VEC>::set(acc, k, 0.f);
+    for (long long j0 = lo; j0 < hi; j0 += kWave) {
+        const int cnt = static_cast<int>(hi - j0 < kWave ? hi - j0 : kWave);      // positions of this block (wave-uniform)
+        const bool mine = lane < cnt;
+        const long long j = j0 + (mine ? lane : cnt - 1);                          // lo <= j < hi <= n
+        // ---- the occurrence's item (every index is checked before an address is formed from it)
+        const int u = sp.inverse[j];
+        const bool u_ok = u >= 0 && u < n;
+        const int uu = u_ok ? u : 0;
+        int s = sp.it_slot[uu];
+        const long long lk = static_cast<long long>(sp.uniq[uu]);
+        int fl = sp.it_flag[uu];
+        const int sg = sp.seg[uu];
+        if (fl & kPosVictim) {      // (LFU policies) the line this batch's own lookup evicts: still in its old slot
+            s = static_cast<int>(sp.rec->vh_slot);
+            fl = (fl & ~kPosInit) | ((fl & kPosVictimHg) ? kPosInit : 0);
+        }
+        const bool bad = !u_ok || s >= c.S || lk >= c.store_rows || sg < 0 || sg >= n;
+        const unsigned long long badm = __ballot(mine && bad);
+        if (badm != 0ull && lane == __builtin_ctzll(badm) && c.ctl->fb_timeout == 0) {
+            c.ctl->fb_timeout = 3;
+            c.ctl->ph[8] = static_cast<unsigned long long>(static_cast<uint32_t>(s));
+            c.ctl->ph[9] = static_cast<unsigned long long>(lk);
+            c.ctl->ph[10] = static_cast<unsigned long long>(static_cast<uint32_t>(fl));
+            c.ctl->ph[11] = static_cast<unsigned long long>(j);
+            c.ctl->ph[12] = static_cast<unsigned long long>(static_cast<uint32_t>(u)) | (static_cast<unsigned long long>(sp.rec->M) << 32);
+            c.ctl->ph[13] = static_cast<unsigned long long>(sp.rec->n) | (static_cast<unsigned long long>(sp.rec->U) << 32);
+            c.ctl->ph[14] = static_cast<unsigned long long>(sp.rec->size);
+            c.ctl->ph[15] = static_cast<unsigned long long>(n);
+        }
+        const bool ok = !bad && s >= 0;      // (s < 0: a key the cache has no line for -- a zero row)
+        // ---- the pull decision, and which occurrence is the key's head
+        const bool is_miss = (fl & kPosMiss) != 0;
+        long long sv = 0, v = -1;
+        int ho = -1;
+        if (ok) {
+            sv = c.srv_ver[lk];
+            if (!is_miss)
+                v = c.line[s].version;
+            ho = sp.perm[sg];
+        }
+        const bool pull = is_miss || v == -1 || sv - v > c.pull_bound;
+        const bool head = ok && mine && static_cast<long long>(ho) == j;
+        if (head && sl == 0)
+            sp.pver[sg] = pull ? sv : kVerKeep;
+        const uint64_t loff = static_cast<uint64_t>(ok ? s : 0) * width;      // float offset of the line's rows
+        const float *src = ok ? (pull ? c.table + static_cast<uint64_t>(lk) * width : c.data + loff) : c.data;
+        const uint64_t sa = reinterpret_cast<uint64_t>(src);
+        const int src_lo = static_cast<int>(static_cast<uint32_t>(sa)), src_hi = static_cast<int>(static_cast<uint32_t>(sa >> 32));
+        const int lof_lo = static_cast<int>(static_cast<uint32_t>(loff)), lof_hi = static_cast<int>(static_cast<uint32_t>(loff >> 32));
+        // the line has a gradient buffer: Line::addup() re-adds it to the pulled row
+        const int rf = (ok ? kSumOk : 0) | ((ok && pull && (fl & kPosInit)) ? kSumGrad : 0) | ((head && pull) ? kSumHead : 0);
+        for (int r0 = 0; r0 < cnt; r0 += ROWS) {
+            V x[ROWS];
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const int tt = r0 + t < cnt ? r0 + t : cnt - 1;
+                const uint64_t a = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(src_hi, tt))) << 32) |
+                                   static_cast<uint32_t>(__builtin_amdgcn_readlane(src_lo, tt));
+                // (a pointer rebuilt from two registers: told to be a GLOBAL one, or the loads would be flat_load)
+                x[t] = *(GlobalV)(a + static_cast<uint64_t>(lcol) * sizeof(float));
+            }
+            // every request of the round is issued before the first add (see bag_sum_kernel)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const bool in = r0 + t < cnt;                                     // wave-uniform
+                const int f = __builtin_amdgcn_readlane(rf, in ? r0 + t : 0);     // wave-uniform
+                V xv = x[t];
+                if (in && (f & (kSumGrad | kSumHead))) {      // a pulled line with a gradient buffer, or the key's head: rare
+                    const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(lof_hi, r0 + t))) << 32) |
+                                       static_cast<uint32_t>(__builtin_amdgcn_readlane(lof_lo, r0 + t));
+                    if (f & kSumGrad) {
+                        const V g = *reinterpret_cast<const V *>(c.grad + o + lcol);
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k)
+                            SumVec<VEC>::set(xv, k, __fadd_rn(SumVec<VEC>::get(xv, k), SumVec<VEC>::get(g, k)));   // data += grad
+                    }
+                    if ((f & kSumHead) && live)
+                        *reinterpret_cast<V *>(c.data + o + col) = xv;
+                }
+                const bool rok = (f & kSumOk) != 0;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float a = SumVec<VEC>::get(acc, k);
+                    const float sum = __fadd_rn(a, rok ? SumVec<VEC>::get(xv, k) : 0.f);
+                    SumVec<VEC>::set(acc, k, in ? sum : a);
+                }
+            }
+        }
+    }
+    // the pooled rows are consumed by another kernel (the dense tower): written around the L2, as bag_sum_kernel's
+    if (live)
+        __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
+}
+
 // ---- the update of a planned batch: ONE launch -----------------------------------------------------------------------------
 // the first kPlanMetaBlocks workgroups: a thread per sorted position, the heads work: the line's version (staged by the
 //     lookup, + updates for a pushed line: cache.cc:171-177; for EVERY line of a push-key batch: cache.cc:321-327), the store's
@@ -1108,8 +1286,11 @@ __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
 // gradient in the spare slot instead of pushing it -- the gradient the reference drops.  Nothing reads it again: the slot stays
 // on the free stack, and every line that takes a slot next is a miss (no kPosInit: its accumulate starts from 0, its lookup
 // adds no gradient) or, call by call, an insert that clears hasgrad.
+// BAGS (ha_cache_update_planned_bags): `grads` is the POOLED gradient [nbags, width]; the source row of occurrence i is its bag
+// -- i / maps.valdiv (fixed bags) or maps.valmap[i] (ragged: bag_of) --, read in place of row i of an expanded [n, width]
+// tensor: the same values in the same order, so the same bits.  The meta and evict roles do not read gradients.
 constexpr int kPlanEvictBlocks = 64, kPlanMetaBlocks = 8;
-template <int VEC>
+template <int VEC, bool BAGS = false>
 __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
     Cache c, const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm, int n, const float *__restrict__ grads,
     ApplyMaps maps, const int32_t *__restrict__ it_upd_pos, const long long *__restrict__ pver,
@@ -1118,8 +1299,9 @@ __global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
     extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
     const int b = blockIdx.x;
     if (b >= kPlanMetaBlocks + kPlanEvictBlocks) {
-        apply_body<kModeSgd, VEC, 2>(c.grad, static_cast<uint64_t>(c.S), static_cast<int>(c.width), sorted, perm, nullptr, n,
-                                     grads, -1.0f, b - kPlanMetaBlocks - kPlanEvictBlocks, s_apply, nullptr, maps);
+        apply_body<kModeSgd, VEC, 2, kHandNone, BAGS>(c.grad, static_cast<uint64_t>(c.S), static_cast<int>(c.width), sorted, perm,
+                                                      nullptr, n, grads, -1.0f, b - kPlanMetaBlocks - kPlanEvictBlocks, s_apply,
+                                                      nullptr, maps);
         return;
     }
     const int lane = lane_id();
@@ -1989,9 +2171,10 @@ static int lookup_rows(ha_cache *h, hipStream_t s, const int4 *pos_item, int64_t
 
 // the row launch of a planned update / of a chain step's push half: the batch's index plan `ws`, its items per sorted position,
 // the versions its lookup staged, the evicted dirty lines to push with it (rec->E of them)
+// (bag >= 1 or bag_of: `grads` is the pooled gradient, see cache_update_planned_kernel's BAGS)
 static int update_rows(ha_cache *h, hipStream_t s, void *ws, int64_t n, const float *grads, const int4 *pos_item,
                        const int32_t *it_upd_pos, const long long *pver, const int32_t *ev_slot, const uint32_t *ev_key,
-                       const int32_t *ev_upd, const PlanRec *rec, int pkmode) {
+                       const int32_t *ev_upd, const PlanRec *rec, int pkmode, int64_t bag = 0, const int32_t *bag_of = nullptr) {
     Cache &c = h->c;
     PlanPtrs p = plan_layout(ws, n);
     const int apply_blocks = static_cast<int>((n + kPosPerBlock - 1) / kPosPerBlock);
@@ -2004,6 +2187,18 @@ static int update_rows(ha_cache *h, hipStream_t s, void *ws, int64_t n, const fl
     const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(grads) % 16 == 0) &&
                         (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
     const dim3 grid(static_cast<unsigned>(apply_blocks + kPlanEvictBlocks + kPlanMetaBlocks));
+    if (bag >= 1 || bag_of != nullptr) {
+        maps.valmap = bag_of;
+        maps.valdiv = bag_of ? 0 : static_cast<int>(bag);
+        if (vec_ok)
+            hipLaunchKernelGGL((cache_update_planned_kernel<4, true>), grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm,
+                               (int)n, grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+        else
+            hipLaunchKernelGGL((cache_update_planned_kernel<1, true>), grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm,
+                               (int)n, grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+        HA_LAUNCH_CHECK();
+        return 0;
+    }
     if (vec_ok)
         hipLaunchKernelGGL(cache_update_planned_kernel<4>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
                            grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
@@ -2067,6 +2262,108 @@ extern "C" int ha_cache_update_planned(ha_cache *h, int64_t n, const float *grad
         if (sl->pp ? chain_push_rows(h, s, sl, i, grads)
                    : update_rows(h, s, sl->ws[i], n, grads, sl->pos_item + at, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at,
                                  sl->ev_key + at, sl->ev_upd + at, sl->rec + i, sl->pk[i] ? 1 : 0))
+            return -1;
+    }
+    cache_mark(h, kTEnd, s);
+    h->settle_slot = nullptr;
+    h->evict_empty = true;
+    return plan_called(h, sl, i, 1, s);
+}
+
+// The lookup of the next planned batch, delivered sum-pooled (cache_lookup_sum_planned_kernel); takes ha_cache_lookup_planned's
+// place in the slot's call sequence and leaves the cache in the same state.
+extern "C" int ha_cache_lookup_sum_planned(ha_cache *h, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
+                                           ha_stream_t stream) {
+    HA_REQUIRE(h, "cache_lookup_sum_planned: null handle");
+    HA_REQUIRE(n >= 0 && nbags >= 0 && nbags < (1ll << 31) && bag >= 0, "cache_lookup_sum_planned: bad sizes n=%ld nbags=%ld bag=%ld",
+               (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "cache_lookup_sum_planned: give exactly one of bag >= 1 and offsets (bag=%ld, "
+               "offsets %s)", (long)bag, offsets ? "given" : "null");
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "cache_lookup_sum_planned: n=%ld is not nbags=%ld bags of "
+               "bag=%ld ids", (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(n == 0 || nbags >= 1, "cache_lookup_sum_planned: %ld ids in no bag", (long)n);
+    HA_REQUIRE(nbags == 0 || out, "cache_lookup_sum_planned: null output");
+    int i = 0;
+    PlanSlot *sl = plan_current(h, 0, &i);
+    HA_REQUIRE(sl == nullptr || !sl->pp, "cache_lookup_sum_planned: the planned block is a push-pull chain (ha_cache_plan_block_push_pull): "
+               "its steps are not pooled -- ha_cache_lookup_planned / ha_cache_push_pull_planned and a pooling pass of the caller's");
+    HA_REQUIRE(!h->chain_open, "cache_lookup_sum_planned: a planned push-pull chain is open: its steps are not pooled");
+    HA_REQUIRE(sl != nullptr, "cache_lookup_sum_planned: no planned batch is due for its lookup (ha_cache_plan_block; lookup and "
+               "update alternate)");
+    HA_REQUIRE(sl->n[i] == n, "cache_lookup_sum_planned: the planned batch has %ld keys (got %ld)", (long)sl->n[i], (long)n);
+    Cache &c = h->c;
+    hipStream_t s = as_stream(stream);
+    if (!sl->waited) {
+        HA_CHECK_HIP(hipStreamWaitEvent(s, sl->booked, 0));
+        sl->waited = true;
+    }
+    cache_mark(h, kTStart, s, true);
+    if (nbags > 0) {
+        const long long at = static_cast<long long>(i) * c.nmax;
+        PlanPtrs p = plan_layout(sl->ws[i], n);
+        SumPlan sp{sl->it_slot + at, sl->it_flag + at, p.uniq, p.inverse, p.seg, p.perm, sl->pver + at, sl->rec + i};
+        const int64_t width = c.width;
+        const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(c.table) % 16 == 0) &&
+                            (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+        // the slice of the 16-byte path: bag_sum_launch's rule (bagsum.hip)
+        int vec = 1;
+        if (vec_ok)
+            for (vec = 4; vec > 1; vec >>= 1)
+                if (kWave * vec <= width && nbags * ((width + kWave * vec - 1) / (kWave * vec)) >= 2048)
+                    break;
+        const uint32_t nslice = static_cast<uint32_t>((width + kWave * vec - 1) / (kWave * vec));
+        const uint64_t blocks64 = (static_cast<uint64_t>(nbags) * nslice + kSumWaves - 1) / kSumWaves;
+        HA_REQUIRE(blocks64 < (1ull << 31), "cache_lookup_sum_planned: batch too large");
+        const int64_t mean = offsets ? (n + nbags - 1) / nbags : bag;
+        const bool few = mean <= 8;
+        const dim3 grid(static_cast<unsigned>(blocks64)), block(kSumWaves * kWave);
+#define HA_SUM_CASE(V, R)                                                                                                     \
+    hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R>), grid, block, 0, s, c, sp, (long long)n, (long long)bag, offsets, \
+                       (long long)nbags, nslice, out)
+        if (vec == 4) {
+            if (few) HA_SUM_CASE(4, 8); else HA_SUM_CASE(4, 32);
+        } else if (vec == 2) {
+            if (few) HA_SUM_CASE(2, 8); else HA_SUM_CASE(2, 32);
+        } else {
+            if (few) HA_SUM_CASE(1, 8); else HA_SUM_CASE(1, 32);
+        }
+#undef HA_SUM_CASE
+        HA_LAUNCH_CHECK();
+    }
+    cache_mark(h, kTEnd, s);
+    h->settle_slot = nullptr;
+    h->settle_idx = i;
+    return plan_called(h, sl, i, 0, s);
+}
+
+// The update of the planned batch from the POOLED gradient [nbags, width]: ha_cache_update_planned on the gradient expanded to
+// [n, width], bit for bit, without the expansion (cache_update_planned_kernel<.., BAGS>).
+extern "C" int ha_cache_update_planned_bags(ha_cache *h, int64_t n, const float *bag_grads, int64_t nbags, int64_t bag,
+                                            const int32_t *bag_of, ha_stream_t stream) {
+    HA_REQUIRE(h, "cache_update_planned_bags: null handle");
+    HA_REQUIRE(n >= 0 && nbags >= 0 && nbags < (1ll << 31) && bag >= 0 && bag < (1ll << 31),
+               "cache_update_planned_bags: bad sizes n=%ld nbags=%ld bag=%ld", (long)n, (long)nbags, (long)bag);
+    // (an empty batch of ragged bags has no bag_of to give: neither is accepted then)
+    HA_REQUIRE(n == 0 ? !(bag >= 1 && bag_of != nullptr) : (bag >= 1) != (bag_of != nullptr),
+               "cache_update_planned_bags: give exactly one of bag >= 1 and bag_of (bag=%ld, bag_of %s)", (long)bag,
+               bag_of ? "given" : "null");
+    HA_REQUIRE(bag < 1 || (n % bag == 0 && n / bag == nbags), "cache_update_planned_bags: n=%ld is not nbags=%ld bags of "
+               "bag=%ld ids", (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(n == 0 || (nbags >= 1 && bag_grads), "cache_update_planned_bags: %ld ids, but no bags or no gradient", (long)n);
+    int i = 0;
+    PlanSlot *sl = plan_current(h, 1, &i);
+    HA_REQUIRE(sl == nullptr || !sl->pp, "cache_update_planned_bags: the planned block is a push-pull chain "
+               "(ha_cache_plan_block_push_pull): its steps are not pooled -- ha_cache_update_planned with the expanded gradient");
+    HA_REQUIRE(!h->chain_open, "cache_update_planned_bags: a planned push-pull chain is open: its steps are not pooled");
+    HA_REQUIRE(sl != nullptr, "cache_update_planned_bags: no planned batch is due for its update (its lookup comes first)");
+    HA_REQUIRE(sl->n[i] == n, "cache_update_planned_bags: the planned batch has %ld keys (got %ld)", (long)sl->n[i], (long)n);
+    Cache &c = h->c;
+    hipStream_t s = as_stream(stream);
+    cache_mark(h, kTStart, s, true);
+    if (n > 0) {
+        const long long at = static_cast<long long>(i) * c.nmax;
+        if (update_rows(h, s, sl->ws[i], n, bag_grads, sl->pos_item + at, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at,
+                        sl->ev_key + at, sl->ev_upd + at, sl->rec + i, sl->pk[i] ? 1 : 0, bag_of ? 0 : bag, bag_of))
             return -1;
     }
     cache_mark(h, kTEnd, s);
@@ -2144,6 +2441,20 @@ extern "C" int ha_cache_run_planned_pairs(ha_cache *h, int count, const int64_t 
         if (ha_cache_lookup_planned(h, n[k], dests[k], stream))
             return -1;
         if (ha_cache_update_planned(h, n[k], grads[k], stream))
+            return -1;
+    }
+    return 0;
+}
+
+// ... with fixed bags of `bag` ids, pooled both ways: ha_cache_lookup_sum_planned into outs[k] ([nbags, width]), then
+// ha_cache_update_planned_bags with bag_grads[k] ([nbags, width]); every pair has n ids
+extern "C" int ha_cache_run_planned_pairs_bags(ha_cache *h, int count, int64_t n, int64_t nbags, int64_t bag, float *const *outs,
+                                               const float *const *bag_grads, ha_stream_t stream) {
+    HA_REQUIRE(h && count >= 0 && (count == 0 || (outs && bag_grads)), "cache_run_planned_pairs_bags: bad arguments");
+    for (int k = 0; k < count; ++k) {
+        if (ha_cache_lookup_sum_planned(h, n, nbags, bag, nullptr, outs[k], stream))
+            return -1;
+        if (ha_cache_update_planned_bags(h, n, bag_grads[k], nbags, bag, nullptr, stream))
             return -1;
     }
     return 0;

@@ -10,7 +10,8 @@ Mirrors (paths relative to /root/reference):
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
-cstable_policy, cache_bound, cache_limit, use_sparse_pull.  The data loader contract is the reference's
+cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and two switches of this build: cache_plan_ahead (the cache's
+planned flow) and cache_fuse_bags (with it, at bsp 0: a sum-pooled lookup is pulled and pushed pooled, see Config).  The data loader contract is the reference's
 `get_arr` / `get_next_arr` (python/hetu/dataloader.py:63-98): `next_ids()` returns the ids of the batch
 after the current one.  Everything computed goes through libherald_amd.so.
 """
@@ -25,17 +26,24 @@ from .sharded import ShardedEmbedding
 
 class Config:
     def __init__(self, comm_mode=None, bsp=0, prefetch=True, cstable_policy=None, cache_bound=100, cache_limit=0,
-                 use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False):
+                 use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False, cache_fuse_bags=True):
         self.comm_mode, self.bsp, self.prefetch = comm_mode, bsp, prefetch
         # not a HetuConfig field: the cache's PLANNED flow (csrc/cache_block.hip) for the bsp-prefetch schedule -- the bookkeeping
         # of batch k + 1 runs on a side stream beside the model's step on batch k.  Needs ids one batch further ahead than
         # get_next_arr gives them: ParameterServerCommunicateOp(..., peek_ids=...); the reference's loader ring is three batches
         # deep (python/hetu/dataloader.py:63-98), so it has them.
         self.cache_plan_ahead = cache_plan_ahead
+        # not a HetuConfig field either: with cache_plan_ahead at bsp 0 (the planned pairs), a communicate op that was told the
+        # bag size of a sum-pooled lookup (ParameterServerCommunicateOp(..., bag=F)) pulls [B, width] pooled rows
+        # (embedding_lookup_sum_planned) and pushes the pooled gradient as it is (embedding_update_planned_bags): no [n, width]
+        # tensor on either side, the same bits.  False: the unfused path (per-occurrence rows, a summing pass, the expanded
+        # gradient).  Every other schedule -- the asp chain, ssp, no prefetch, world > 1, the call-by-call cache -- is unfused.
+        self.cache_fuse_bags = cache_fuse_bags
         self.cstable_policy, self.cache_bound, self.cache_limit = cstable_policy, cache_bound, cache_limit
         self.use_sparse_pull = use_sparse_pull
         self.cache_perf_enable = cache_perf_enable        # executor.py: cache_perf_enable (run_hetu.py:508-515 dumps the dicts)
         self.ps_map = {}
+        self.ps_pooled = {}           # parameter -> bag size: its ps_map buffer holds POOLED rows [B, width]
 
 
 class EmbeddingParameter:
@@ -122,7 +130,8 @@ class EmbeddingLookUpSum(EmbeddingLookUp):
     offsets[B + 1] for ragged bags.  With a device table it is the fused kernel (ops.embedding_lookup_sum).  On the PS, cache
     and prefetched paths the per-occurrence rows arrive as EmbeddingLookUp delivers them and the same kernel sums them, in the
     same position order, out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Those paths are
-    not fused: they still move [n, width] rows."""
+    not fused: they still move [n, width] rows -- except the cache's planned pairs (Config.cache_fuse_bags), where the
+    communicate op's buffer already holds the pooled rows (the cache summed them as it read them) and is copied as it is."""
 
     def forward_hook(self, config):
         super().forward_hook(config)
@@ -134,6 +143,12 @@ class EmbeddingLookUpSum(EmbeddingLookUp):
     def _compute_sum(self, ids, output_val, stream=None, offsets=None):
         if self._fused:
             return ops.embedding_lookup_sum(self.embedding.table, ids, offsets=offsets, out=output_val, stream=stream)
+        if self._rows_compute == self._compute_prefetched and \
+                getattr(self.config, "ps_pooled", {}).get(self.embedding) is not None:
+            if offsets is not None or ids.dim() != 2 or ids.shape[1] != self.config.ps_pooled[self.embedding]:
+                raise ValueError("EmbeddingLookUpSum: the communicate op pulls pooled rows for fixed bags of %d ids"
+                                 % self.config.ps_pooled[self.embedding])
+            return self._compute_prefetched(ids, output_val, stream)      # a pooled buffer, as it is
         n, width = ids.numel(), self.embedding.shape[1]
         if self._pos is None or self._pos.numel() < n or self._pos.device != output_val.device:
             self._pos = torch.arange(max(n, 1), dtype=torch.int64, device=output_val.device)
@@ -186,14 +201,19 @@ def sgd_update_sparse(param, grad, lr, stream=None):
 
 
 class ParameterServerCommunicateOp:
-    def __init__(self, parameter, learning_rate, next_ids, peek_ids=None):
+    def __init__(self, parameter, learning_rate, next_ids, peek_ids=None, bag=None):
         """peek_ids(j) (optional, Config.cache_plan_ahead): the ids of the batch j batches after the one next_ids() returns
-        (peek_ids(0) = that batch itself), without advancing the loader; None when there is none."""
+        (peek_ids(0) = that batch itself), without advancing the loader; None when there is none.
+        bag (optional): the embedding is read through a sum-pooled lookup (EmbeddingLookUpSum) with fixed bags of `bag` ids --
+        ids arrive as [B, bag].  With the cache's planned pairs and Config.cache_fuse_bags the op then keeps sparse_pull_val as
+        [B, width] and moves pooled rows and pooled gradients only; on every other schedule it changes nothing."""
         self.parameter = parameter
         self.learning_rate = -learning_rate                           # :24
         self.next_ids = next_ids
         self.peek_ids = peek_ids
         self._peek_offset = 1
+        self.bag = int(bag) if bag is not None else None
+        self._bag = None              # the bag size while the pooled planned pairs are in use (forward_hook decides)
         self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
         self._chain = False           # the planned flow of the asp schedule: _planned = ids of a push-pull chain's batches
 
@@ -234,6 +254,8 @@ class ParameterServerCommunicateOp:
                 self.compute = self._compute_bsp_prefetch
                 if getattr(config, "cache_plan_ahead", False) and store.world == 1 and self.peek_ids is not None:
                     self._planned = []        # pull(k + 1) follows push(k) of the same ids batch after batch: the planned pairs
+                    if self.bag is not None and getattr(config, "cache_fuse_bags", True):
+                        self._bag = self.bag
             elif config.prefetch:
                 self.compute = self._compute_asp_prefetch
                 if getattr(config, "cache_plan_ahead", False) and store.world == 1 and self.peek_ids is not None and \
@@ -257,8 +279,15 @@ class ParameterServerCommunicateOp:
             ids = first_ids if first_ids is not None else self.next_ids()
             # a laia data loader hands over (ids, push plan): cstable.py:49 (the planned flow plans the batch with its plan)
             first = ids[0] if isinstance(ids, tuple) else ids
-            self.sparse_pull_val = torch.empty(tuple(first.shape) + (p.shape[1],), dtype=torch.float32,
-                                               device=first.device)
+            if self._bag is not None:
+                if first.dim() != 2 or first.shape[1] != self._bag:
+                    raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
+                                     % (self._bag, self._bag, tuple(first.shape)))
+                self.sparse_pull_val = torch.empty((first.shape[0], p.shape[1]), dtype=torch.float32, device=first.device)
+                config.ps_pooled[p] = self._bag
+            else:
+                self.sparse_pull_val = torch.empty(tuple(first.shape) + (p.shape[1],), dtype=torch.float32,
+                                                   device=first.device)
             if self._planned is None:
                 ids = first
             # (peek_ids counts from the batch next_ids() returns: an explicit first batch is the one before it)
@@ -267,12 +296,15 @@ class ParameterServerCommunicateOp:
             self._peek_offset = 1
 
     # -- compute variants (:37-56)
-    @staticmethod
-    def _per_occurrence(grad):
+    def _per_occurrence(self, grad):
         """Pooled slices (the gradient of EmbeddingLookUpSum: one row per bag) are expanded to per-occurrence values before
         they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The PS, cache and
-        step-engine paths are NOT fused for pooled access: they move the expanded [n, width] values as they always did."""
+        step-engine paths are NOT fused for pooled access: they move the expanded [n, width] values as they always did.  The
+        cache's planned pairs are (Config.cache_fuse_bags): slices pooled by the op's own bag size stay [B, width]; -lr is
+        applied to those rows only, which is the same product for every occurrence of a bag."""
         if not getattr(grad, "pooled", False):
+            return grad
+        if self._bag is not None and grad.bag == self._bag:
             return grad
         return ops.IndexedSlices(indices=grad.indices, values=grad.expanded_values(), dense_shape=grad.dense_shape,
                                  push_indices=grad.push_indices)
@@ -326,6 +358,8 @@ class ParameterServerCommunicateOp:
                 raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead): the gradients pushed are not those of the "
                                    "batch pulled last, or not with the push plan it was planned with")
             self._planned.pop(0)
+            if self._bag is not None and getattr(grad, "pooled", False):      # vals is [B, width]: one row per bag
+                return self.cache.embedding_update_planned_bags(vals.contiguous(), bag=self._bag)
             return self.cache.embedding_update_planned(vals)     # (a planned plan: cache.cc:248-335, _embeddingUpdateWithPushKeys)
         if grad.push_indices is None:
             # The executor pushes the gradients of the batch it looked up last (bsp / ssp: push(k) follows pull(k) as the
@@ -372,6 +406,8 @@ class ParameterServerCommunicateOp:
             nxt = self.peek_ids(self._peek_offset)                 # the batch after this one: its bookkeeping runs from now on,
             if nxt is not None:                                    # beside this batch's rows and the model's step
                 self._plan(nxt)
+            if self._bag is not None:
+                return self.cache.embedding_lookup_sum_planned(dest, bag=self._bag)
             return self.cache.embedding_lookup_planned(dest)      # (no next batch: the next pull plans for itself)
         if isinstance(ids, tuple):              # (ids, push plan) of a laia-scheduled batch (cstable.py:49)
             ids = ids[0]

@@ -945,6 +945,38 @@ int ha_cache_plan_pending(ha_cache *cache);
 /* `count` planned pairs by one call: ha_cache_lookup_planned(n[k], dests[k]) then ha_cache_update_planned(n[k], grads[k]) */
 int ha_cache_run_planned_pairs(ha_cache *cache, int count, const int64_t *n, float *const *dests, const float *const *grads,
                                ha_stream_t stream);
+/* SUM-POOLED access in the planned flow (csrc/cache_block.hip): the embedding_lookup_op + reduce_sum_op(axes=1) pair of the
+ * reference's emb_sum_* models over a cached table, without the per-occurrence [n, width] tensors on either side.  Bags as
+ * ha_gather_sum_*: fixed -- bag >= 1, offsets == NULL, n == nbags * bag, occurrence i belongs to bag i / bag -- or ragged -- a
+ * device int64 offsets[nbags + 1], every entry clamped to [0, n] and every bag's end to its start, so nothing outside the
+ * batch is read and nothing outside out[nbags, width] written, whatever offsets holds.  Exactly one of the two.
+ *
+ * ha_cache_lookup_sum_planned: the lookup of the next planned batch, delivered pooled.  With r_j the row
+ * ha_cache_lookup_planned would have written for occurrence j: out[b,:] = ((0.0f + r_lo) + r_lo+1) + ... in position order, one
+ * __fadd_rn per term -- bit for bit ha_cache_lookup_planned followed by ha_gather_sum over the ids 0 .. n-1.  An empty bag is
+ * zeros; a key the cache has no line for adds +0.0f.  It takes ha_cache_lookup_planned's place in the block's call sequence
+ * (same order, same wait for the bookkeeping, same ha_cache_perf record), and every side effect on the cache is that lookup's:
+ * the line of a pulled key (a miss, version -1, or a store version ahead by more than pull_bound) is refreshed with the store
+ * row (+ the line's gradient row, Line::addup) and its version staged for the update.  The refresh is made by the waves whose
+ * bag holds the key's first occurrence: every occurrence must lie in a bag (offsets[0] <= 0, offsets[nbags] >= n, entries
+ * non-decreasing), or the lines whose first occurrence lies in none are not refreshed.
+ *
+ * ha_cache_update_planned_bags: the update of the planned batch from the POOLED gradient bag_grads[nbags, width]: occurrence i
+ * takes row i / bag (bag >= 1, bag_of == NULL, n == nbags * bag) or row bag_of[i] (device int32 [n] with entries in [0, nbags),
+ * from ha_bag_of; bag == 0) -- exactly one of the two, as ha_sgd_apply_bags (n == 0: bag_of may be NULL).  Bit for bit ha_cache_update_planned on the
+ * gradient expanded to [n, width], in bound mode and in push-key mode; it takes that call's place in the sequence.
+ *
+ * The state either pooled call leaves is the state its unpooled counterpart leaves, so a pooled lookup may be followed by an
+ * unpooled update and the other way round.  The steps of a push-pull chain (ha_cache_plan_block_push_pull) are not pooled:
+ * both calls refuse such a block, and an open chain, before anything is enqueued. */
+int ha_cache_lookup_sum_planned(ha_cache *cache, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
+                                ha_stream_t stream);
+int ha_cache_update_planned_bags(ha_cache *cache, int64_t n, const float *bag_grads, int64_t nbags, int64_t bag,
+                                 const int32_t *bag_of, ha_stream_t stream);
+/* `count` planned pairs of n ids in fixed bags by one call: ha_cache_lookup_sum_planned(n, nbags, bag, NULL, outs[k]) then
+ * ha_cache_update_planned_bags(n, bag_grads[k], nbags, bag, NULL) */
+int ha_cache_run_planned_pairs_bags(ha_cache *cache, int count, int64_t n, int64_t nbags, int64_t bag, float *const *outs,
+                                    const float *const *bag_grads, ha_stream_t stream);
 /* The planned flow of a PUSH-PULL CHAIN: CacheBase::_embeddingPushPull (cache.cc:356-422), the one cache call per step of the
  * asp-with-prefetch schedule (python/hetu/gpu_ops/ParameterServerCommunicate.py:37-40, 68-72): step = push_pull(pull = the ids of
  * batch k + 1, push = the ids and gradients of batch k).  LRU over a local store only (the LFU policies' planned bookkeeping
