@@ -39,6 +39,10 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      gradient expanded before the push -- except --embedding cache --cache-planned --bsp 0, where the
                      cache's planned pairs are pooled as well (ha_cache_lookup_sum_planned /
                      ha_cache_update_planned_bags).  The step engines refuse the model.
+  --optimizer        the embedding table's optimizer on --embedding hbm: sgd (default), momentum, nesterov, adagrad, adam or adamw
+                     with the reference's default hyper-parameters (python/hetu/optimizer.py:232-483); the states live beside
+                     the table.  A pooled model's gradient goes to the optimizer pooled as well (ha_sparse_opt_fused_bags_*,
+                     ha_momentum_sparse_update_bags_*).  The dense tower keeps SGD.  Every other engine runs sparse SGD only.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -120,6 +124,7 @@ class SumTower(Tower):
 
 
 POOLED_MODELS = ("emb_sum_wdl",)
+OPTIMIZERS = ("sgd", "momentum", "nesterov", "adagrad", "adam", "adamw")
 
 
 def make_tower(model, width, seed=0):
@@ -240,7 +245,8 @@ def make_batches(nbatch, batch, rows, seed=0, rank=0, world=1):
 
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
-          bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True):
+          bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
+          opt_fuse_bags=True):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -251,9 +257,18 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     (cache_fuse_bags=False: the unfused path, the same bits).
     The ring wraps round, so the chain is still open when training ends, with one step's bookkeeping planned ahead and never
     run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
-    replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests)."""
+    replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests).
+    optimizer (--optimizer): the embedding table's optimizer, --embedding hbm only -- sgd, momentum, nesterov, adagrad, adam or
+    adamw with the reference's defaults (momentum 0.9; beta 0.9 / 0.999, eps 1e-7, accumulator from 0, weight decay 0); the
+    tower keeps SGD.  opt_fuse_bags=False: the reference's own sequence for it (expanded gradient, deduplicate, the symbol) --
+    the same bits."""
     dev = torch.device(device)
     pooled = model in POOLED_MODELS
+    if optimizer not in OPTIMIZERS:
+        raise ValueError("optimizer must be one of %s, got %r" % (", ".join(OPTIMIZERS), optimizer))
+    if optimizer != "sgd" and embedding != "hbm":
+        raise ValueError("--optimizer %s is applied to the embedding table on --embedding hbm only; --embedding %s runs sparse "
+                         "SGD" % (optimizer, embedding))
     if pooled and embedding in ("step", "step3", "queue"):
         raise ValueError("--model %s pools its embeddings (sum over a sample's 26 rows): the step engines (--embedding step, "
                          "step3, queue) deliver and update per-occurrence rows only; use --embedding hbm (fused), ps or cache"
@@ -303,6 +318,31 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
         lookup = hetu_ops.EmbeddingLookUp(param)
         lookup_grad = hetu_ops.EmbeddingLookUp_Gradient(param.shape)
     lookup.forward_hook(config)
+
+    # the embedding optimizer's states, allocated beside the table (zeros: the reference's initial values)
+    opt_state = None
+    if optimizer != "sgd":
+        opt_state = {"s1": torch.zeros_like(param.table), "beta1t": 1.0, "beta2t": 1.0}
+        if optimizer in ("adam", "adamw"):
+            opt_state["s2"] = torch.zeros_like(param.table)
+
+    def embedding_update(grad):
+        if optimizer == "sgd":
+            hetu_ops.sgd_update_sparse(param, grad, lr)            # OptimizerOp, sparse SGD branch
+        elif optimizer in ("momentum", "nesterov"):
+            hetu_ops.momentum_update_sparse(param, grad, opt_state["s1"], lr, 0.9, optimizer == "nesterov",
+                                            fuse_bags=opt_fuse_bags)
+        elif optimizer == "adagrad":
+            hetu_ops.adagrad_update_sparse(param, grad, opt_state["s1"], lr, 1e-7, fuse_bags=opt_fuse_bags)
+        else:
+            opt_state["beta1t"] *= 0.9                             # once per step, before the update (optimizer.py:384, 456)
+            opt_state["beta2t"] *= 0.999
+            args = (param, grad, opt_state["s1"], opt_state["s2"], lr, 0.9, 0.999, opt_state["beta1t"], opt_state["beta2t"],
+                    1e-7)
+            if optimizer == "adam":
+                hetu_ops.adam_update_sparse(*args, fuse_bags=opt_fuse_bags)
+            else:
+                hetu_ops.adamw_update_sparse(*args, 0.0, fuse_bags=opt_fuse_bags)
 
     fused = None
     if embedding == "step":
@@ -360,7 +400,7 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                               fused["pends"][k % 2], ids_of(k + 1).reshape(-1), fused["plans"][(k + 1) % 2],
                               fused["pends"][(k + 1) % 2], next_out=fused["outs"][(k + 1) % 2])
         elif comm is None:
-            hetu_ops.sgd_update_sparse(param, grad, lr)            # OptimizerOp, sparse SGD branch
+            embedding_update(grad)                                 # OptimizerOp's sparse branch of --optimizer
         else:
             comm.compute(grad)                                     # -lr scale, push, (barrier), pull of batch k+1
         losses.append(float(loss.detach()))       # synchronises: a cheap place to poll the hand-off flag
@@ -432,6 +472,8 @@ def main():
     ap.add_argument("--nepoch", type=int, default=-1, help="epochs of `--steps` steps each (default: one)")
     ap.add_argument("--embedding", choices=["hbm", "step", "step3", "queue", "ps", "cache"], default=None,
                     help="this build's engine names; default: from --comm / --cache")
+    ap.add_argument("--optimizer", choices=list(OPTIMIZERS), default="sgd",
+                    help="the embedding table's optimizer (--embedding hbm only; the tower keeps SGD)")
     ap.add_argument("--rows", type=int, default=33762577)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--lr", type=float, default=0.1)
@@ -454,6 +496,8 @@ def main():
     if args.embedding is None:
         args.embedding = "hbm" if comm is None else ("cache" if args.cache else "ps")
     args.cache = policy
+    if args.optimizer != "sgd" and (args.laia or args.embedding != "hbm"):
+        ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
     if args.nepoch > 0:
         args.steps *= args.nepoch
     cache_limit = max(int(args.cache_limit_ratio * args.rows), args.batch * NFIELD)
@@ -470,7 +514,7 @@ def main():
         losses = train(args.embedding, args.rows, args.width, args.batch, args.steps, args.lr, args.cache,
                        args.bound, cache_limit=cache_limit, device="cuda:%d" % local_rank,
                        log_every=max(1, args.steps // 10), model=args.model, bsp=args.bsp if comm is not None else 0,
-                       cache_perf=args.cache_perf, cache_planned=args.cache_planned)[0]
+                       cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer)[0]
     if local_rank == 0:
         print("first 10 steps: loss %.5f   last 10 steps: loss %.5f" % (np.mean(losses[:10]), np.mean(losses[-10:])))
 

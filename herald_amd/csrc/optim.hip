@@ -278,6 +278,31 @@ extern "C" int AddL2RegularizationSparse(const DLArrayHandle param, const DLArra
                            dl_stream(stream_handle));
 }
 
+// dense second phase of the momentum update over the whole table (momentum_dense_kernel)
+static int momentum_dense(float *p, float *v, int64_t rows, int64_t width, float momentum, bool nesterov, hipStream_t stream) {
+    const uint64_t total = static_cast<uint64_t>(rows) * static_cast<uint64_t>(width);
+    if (total == 0)
+        return 0;
+    const bool vec = reinterpret_cast<uintptr_t>(p) % 16 == 0 && reinterpret_cast<uintptr_t>(v) % 16 == 0;
+    const uint64_t nvec = vec ? total / 4 : total;
+    uint64_t blocks = (nvec + 255) / 256;
+    if (blocks > 65536)
+        blocks = 65536;
+    if (blocks == 0)
+        blocks = 1;
+    const dim3 grid(static_cast<unsigned>(blocks)), block(256);
+    if (vec && nesterov)
+        hipLaunchKernelGGL((momentum_dense_kernel<true, 4>), grid, block, 0, stream, p, v, momentum, nvec, total);
+    else if (vec)
+        hipLaunchKernelGGL((momentum_dense_kernel<false, 4>), grid, block, 0, stream, p, v, momentum, nvec, total);
+    else if (nesterov)
+        hipLaunchKernelGGL((momentum_dense_kernel<true, 1>), grid, block, 0, stream, p, v, momentum, nvec, total);
+    else
+        hipLaunchKernelGGL((momentum_dense_kernel<false, 1>), grid, block, 0, stream, p, v, momentum, nvec, total);
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
 // src/ops/OptimizersSparse.cu:101-231.  First phase (ids may repeat): velocity[id,:] += -lr * g per
 // occurrence (Nesterov: param[id,:] too) -- here in occurrence order through the index plan instead of
 // float atomics; acc - lr*g is bit for bit acc + (-lr*g).  Second phase: dense, over the whole table.
@@ -304,27 +329,61 @@ extern "C" int MomentumOptimizerSparseUpdate(DLArrayHandle param, const DLArrayH
         if (nesterov && ha_sgd_apply(p, rows, width, ws, n, g, lr, stream))
             return -1;
     }
-    const uint64_t total = static_cast<uint64_t>(rows) * static_cast<uint64_t>(width);
-    if (total == 0)
-        return 0;
-    const bool vec = reinterpret_cast<uintptr_t>(p) % 16 == 0 && reinterpret_cast<uintptr_t>(v) % 16 == 0;
-    const uint64_t nvec = vec ? total / 4 : total;
-    uint64_t blocks = (nvec + 255) / 256;
-    if (blocks > 65536)
-        blocks = 65536;
-    if (blocks == 0)
-        blocks = 1;
-    const dim3 grid(static_cast<unsigned>(blocks)), block(256);
-    if (vec && nesterov)
-        hipLaunchKernelGGL((momentum_dense_kernel<true, 4>), grid, block, 0, stream, p, v, momentum, nvec, total);
-    else if (vec)
-        hipLaunchKernelGGL((momentum_dense_kernel<false, 4>), grid, block, 0, stream, p, v, momentum, nvec, total);
-    else if (nesterov)
-        hipLaunchKernelGGL((momentum_dense_kernel<true, 1>), grid, block, 0, stream, p, v, momentum, nvec, total);
-    else
-        hipLaunchKernelGGL((momentum_dense_kernel<false, 1>), grid, block, 0, stream, p, v, momentum, nvec, total);
-    HA_LAUNCH_CHECK();
-    return 0;
+    return momentum_dense(p, v, rows, width, momentum, nesterov, stream);
+}
+
+// The one-call form on POOLED gradients (sum-pooled lookup, bagsum.hip): the first phase is ha_sgd_apply_bags -- occurrence i
+// takes the row of its bag, nothing is expanded --, the second the same dense pass.  Bit for bit MomentumOptimizerSparseUpdate on
+// bag_grads expanded to [n, width], in tolerance mode too (ha_sgd_apply_bags equals ha_sgd_apply there as well).
+template <typename IdT>
+static int momentum_sparse_update_bags(const char *what, float *param, int64_t rows, int64_t width, const IdT *ids, int64_t n,
+                                       const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                       float *velocity, float lr, float momentum, int nesterov, ha_stream_t stream) {
+    HA_REQUIRE(rows >= 0 && width >= 1 && width < (1ll << 30) && n >= 0 && n < (1ll << 31) && nbags >= 0 && bag >= 0 &&
+                   nbags < (1ll << 31),
+               "%s: bad sizes rows=%ld width=%ld n=%ld bag=%ld nbags=%ld", what, (long)rows, (long)width, (long)n, (long)bag,
+               (long)nbags);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld)", what, (long)bag);
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+               (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(param && velocity && (n == 0 || (ids && bag_grads && nbags >= 1)), "%s: null pointer or no bags", what);
+    hipStream_t s = as_stream(stream);
+    if (n > 0) {
+        const size_t plan_bytes = align_up(ha_plan_bytes(n), 256);
+        void *ws = nullptr;
+        if (scratch_get(s, plan_bytes + (offsets ? static_cast<size_t>(n) * 4 : 0), &ws))
+            return -1;
+        int32_t *bag_of = nullptr;
+        if (offsets) {
+            bag_of = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + plan_bytes);
+            if (ha_bag_of(offsets, nbags, n, bag_of, stream))
+                return -1;
+        }
+        if (sizeof(IdT) == 4 ? ha_plan_sort_f32ids(reinterpret_cast<const float *>(ids), n, ws, stream)
+                             : ha_plan_sort_u64ids(reinterpret_cast<const uint64_t *>(ids), n, ws, stream))
+            return -1;
+        if (ha_sgd_apply_bags(velocity, rows, width, ws, n, bag_grads, offsets ? 0 : bag, bag_of, lr, stream))
+            return -1;
+        if (nesterov && ha_sgd_apply_bags(param, rows, width, ws, n, bag_grads, offsets ? 0 : bag, bag_of, lr, stream))
+            return -1;
+    }
+    return momentum_dense(param, velocity, rows, width, momentum, nesterov != 0, s);
+}
+
+extern "C" int ha_momentum_sparse_update_bags_f32ids(float *param, int64_t rows, int64_t width, const float *ids, int64_t n,
+                                                     const float *bag_grads, int64_t bag, const int64_t *offsets,
+                                                     int64_t nbags, float *velocity, float lr, float momentum, int nesterov,
+                                                     ha_stream_t stream) {
+    return momentum_sparse_update_bags<float>("ha_momentum_sparse_update_bags_f32ids", param, rows, width, ids, n, bag_grads,
+                                              bag, offsets, nbags, velocity, lr, momentum, nesterov, stream);
+}
+
+extern "C" int ha_momentum_sparse_update_bags_u64ids(float *param, int64_t rows, int64_t width, const uint64_t *ids, int64_t n,
+                                                     const float *bag_grads, int64_t bag, const int64_t *offsets,
+                                                     int64_t nbags, float *velocity, float lr, float momentum, int nesterov,
+                                                     ha_stream_t stream) {
+    return momentum_sparse_update_bags<uint64_t>("ha_momentum_sparse_update_bags_u64ids", param, rows, width, ids, n, bag_grads,
+                                                 bag, offsets, nbags, velocity, lr, momentum, nesterov, stream);
 }
 
 extern "C" int AdaGradOptimizerSparseUpdate(DLArrayHandle param, const DLArrayHandle grad_indices,

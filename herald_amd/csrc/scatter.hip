@@ -87,7 +87,9 @@ __global__ __launch_bounds__(1024, 8) void apply_mapped2_kernel(
 // batch sit inside long runs, so here a fixed grid of workgroups loops over the unique keys instead
 // (uniq / seg / counts of the plan): short and medium runs are applied by the wave that owns the key,
 // keys with >= kLongRun occurrences are collected in a list ...
-template <int MODE, int VEC>
+// BAGS (kModeOpt on pooled gradients, ha_sparse_opt_fused_bags_*): the source row of an occurrence goes through
+// ApplyMaps::valmap / valdiv in every run class (src_row, scatter_dev.h); false compiles to what it always was.
+template <int MODE, int VEC, bool BAGS = false>
 __global__ __launch_bounds__(1024, 8) void apply_unique_kernel(
     float *__restrict__ dst, uint64_t dst_rows, int width, PlanHeader *__restrict__ hdr,
     const uint32_t *__restrict__ uniq, const int32_t *__restrict__ seg,
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(1024, 8) void apply_unique_kernel(
         if (row >= dst_rows)
             continue;  // out-of-range id: ignored
         float *dst_row = dst + row * static_cast<uint64_t>(width);
-        const int pv = perm[min(s + lane, n - 1)];   // lanes 0 .. len-1: the run's occurrence indices
+        const int pv = src_row<BAGS>(perm[min(s + lane, n - 1)], maps);   // lanes 0 .. len-1: the run's occurrence indices
         Second d2{nullptr, false};
         if (MODE == kModeOpt)
             opt_rows(d2, maps, row, width);
@@ -132,7 +134,7 @@ __global__ __launch_bounds__(1024, 8) void apply_unique_kernel(
 // ... and served here: work item = (long key, 64-column slice); the 16 waves of a workgroup load the
 // occurrence rows of the slice block by block into LDS and one wave runs the ordered chain
 // (coop_slices, scatter_dev.h).
-template <int MODE>
+template <int MODE, bool BAGS = false>
 __global__ __launch_bounds__(1024, 8) void apply_long_kernel(
     float *__restrict__ dst, uint64_t dst_rows, int width, const PlanHeader *__restrict__ hdr,
     const uint32_t *__restrict__ uniq, const int32_t *__restrict__ seg,
@@ -150,8 +152,9 @@ __global__ __launch_bounds__(1024, 8) void apply_long_kernel(
             Second d2{nullptr, false};
             if (MODE == kModeOpt)
                 opt_rows(d2, maps, row, width);
-            coop_slices<MODE, false>(dst + row * static_cast<uint64_t>(width), true, d2, grads, perm, maps, n, lr,
-                                     seg[u], counts[u], width, j, nslice, w, reinterpret_cast<float *>(s_apply));
+            coop_slices<MODE, false, kHandNone, BAGS>(dst + row * static_cast<uint64_t>(width), true, d2, grads, perm, maps, n,
+                                                      lr, seg[u], counts[u], width, j, nslice, w,
+                                                      reinterpret_cast<float *>(s_apply));
         }
         __syncthreads();
     }
@@ -232,7 +235,7 @@ __global__ __launch_bounds__(1024) void apply_chunk_plan_kernel(const PlanHeader
     }
 }
 
-template <int MODE, int VEC>
+template <int MODE, int VEC, bool BAGS = false>
 __global__ __launch_bounds__(1024, 8) void apply_listed_kernel(
     float *__restrict__ dst, uint64_t dst_rows, int width, const PlanHeader *__restrict__ hdr,
     const uint32_t *__restrict__ uniq, const int32_t *__restrict__ seg,
@@ -347,14 +350,14 @@ __global__ __launch_bounds__(1024, 8) void apply_listed_kernel(
                 if (MODE != kModeOpt && maps.tree_from > 0 && kl >= maps.tree_from && (width & 3) == 0 &&
                     ((reinterpret_cast<uintptr_t>(dst_row) | reinterpret_cast<uintptr_t>(grads)) & 15) == 0) {
                     // (coop_slices' own condition for the tree; ends with a barrier)
-                    coop_slice_tree<MODE>(dst_row, init, grads, perm, maps, n, lr, ks, kl, width, j, w,
-                                          reinterpret_cast<float *>(s_apply), p_cur, true);
+                    coop_slice_tree<MODE, BAGS>(dst_row, init, grads, perm, maps, n, lr, ks, kl, width, j, w,
+                                                reinterpret_cast<float *>(s_apply), p_cur, true);
                 } else {
                     Second d2{nullptr, false};
                     if (MODE == kModeOpt)
                         opt_rows(d2, maps, row, width);
-                    coop_slices<MODE, false>(dst_row, init, d2, grads, perm, maps, n, lr, ks, kl, width, j, nslice, w,
-                                             reinterpret_cast<float *>(s_apply));
+                    coop_slices<MODE, false, kHandNone, BAGS>(dst_row, init, d2, grads, perm, maps, n, lr, ks, kl, width, j, nslice,
+                                                              w, reinterpret_cast<float *>(s_apply));
                     __syncthreads();
                 }
             }
@@ -388,7 +391,7 @@ __global__ __launch_bounds__(1024, 8) void apply_listed_kernel(
         for (int k = 0; k < cnt; ++k) {
             const int u = static_cast<int>(ub) + k * nwaves;
             const int len = __builtin_amdgcn_readlane(m_len, k);
-            const int pv = pv_next;   // lanes 0 .. len-1: the run's occurrence indices
+            const int pv_raw = pv_next;   // lanes 0 .. len-1: the run's occurrence indices
             if (k + 1 < cnt)
                 pv_next = perm[min(__builtin_amdgcn_readlane(m_s, k + 1) + lane, n - 1)];
             if (len >= kLongRun)
@@ -405,6 +408,9 @@ __global__ __launch_bounds__(1024, 8) void apply_listed_kernel(
             if (row >= dst_rows)
                 continue;  // out-of-range id / no destination: ignored
             float *dst_row = dst + row * static_cast<uint64_t>(width);
+            // (BAGS: mapped here, not where the indices are asked for -- the division would wait for that load in front of the
+            // current key's rows)
+            const int pv = src_row<BAGS>(pv_raw, maps);
             Second d2{nullptr, false};
             if (MODE == kModeOpt)
                 opt_rows(d2, maps, row, width);
@@ -501,26 +507,30 @@ static int apply_launch(float *dst, int64_t dst_rows, int64_t width,
 
 // apply of a FINISHED plan by unique key (larger batches); plan scratch keys_alt holds the long list
 namespace ha {
-template <int MODE>
-int apply_by_unique(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, int64_t n,
-                    const float *grads, float lr, hipStream_t stream, ApplyMaps maps) {
+// BAGS: the kernels' BAGS instantiations (source rows through maps.valmap / maps.valdiv; kModeOpt only)
+template <int MODE, bool BAGS>
+static int apply_by_unique_impl(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, int64_t n,
+                                const float *grads, float lr, hipStream_t stream, ApplyMaps maps) {
     HA_REQUIRE(dst && plan_ws && grads && n > 0 && width >= 1 && width < (1 << 30), "apply_by_unique: bad arguments");
     if (maps.tree_from == 0)
         maps.tree_from = tolerance_tree_from();
     PlanPtrs p = plan_layout(plan_ws, n);
+    // (kModeOpt: the epilogue moves the state rows with the same 16-byte accesses)
     const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0) &&
-                        (reinterpret_cast<uintptr_t>(grads) % 16 == 0);
+                        (reinterpret_cast<uintptr_t>(grads) % 16 == 0) &&
+                        (MODE != kModeOpt || ((reinterpret_cast<uintptr_t>(maps.opt_s1) % 16 == 0) &&
+                                              (reinterpret_cast<uintptr_t>(maps.opt_s2) % 16 == 0)));
     const dim3 grid(512), block(1024);   // two workgroups per compute unit, looping over the keys
     if (n > kSmallMax && n <= kFinishChunkedMax) {
         // tolerance mode: runs beyond 256 occurrences in chunks (see apply_listed_kernel); scratch = radix scratch of the plan
         // (perm_alt: offsets and counters) and its `dep` words (chunk sums)
         ChunkPlan cp{nullptr, nullptr, nullptr};
         const int nslice = static_cast<int>((width + kWave - 1) / kWave);
-        const bool plain = !maps.rowmap && !maps.valmap && !maps.dst_init && MODE != kModeOpt;
+        const bool plain = !maps.rowmap && !maps.valmap && !maps.dst_init && MODE != kModeOpt && !BAGS;
         if (g_tree_chunks && maps.tree_from > 0 && plain && vec_ok && nslice <= 4) {
             static DeviceOnce lds_allowed;
             if (lds_allowed.run([]() -> int {
-                    HA_ALLOW_LDS((apply_listed_kernel<MODE, 4>), kListedLdsBytes);
+                    HA_ALLOW_LDS((apply_listed_kernel<MODE, 4, BAGS>), kListedLdsBytes);
                     return 0;
                 }))
                 return -1;
@@ -535,11 +545,11 @@ int apply_by_unique(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, 
         // 57.8 / 57.2 / 59.0 us alone against 52.5 us, and no faster together -- tools/cfgc_bench.py)
         const dim3 grid2(1024);      // (apply_listed_kernel: up to 512 workgroups of listed items in front of 512 of keys)
         if (vec_ok)
-            hipLaunchKernelGGL((apply_listed_kernel<MODE, 4>), grid2, block, cp.meta ? kListedLdsBytes : kApplyLdsBytes, stream,
+            hipLaunchKernelGGL((apply_listed_kernel<MODE, 4, BAGS>), grid2, block, cp.meta ? kListedLdsBytes : kApplyLdsBytes, stream,
                                dst, (uint64_t)dst_rows, (int)width, p.hdr, p.uniq, p.seg, p.counts, p.perm, (int)n, grads,
                                lr, p.keys_alt, maps, cp);
         else
-            hipLaunchKernelGGL((apply_listed_kernel<MODE, 1>), grid2, block, kApplyLdsBytes, stream, dst,
+            hipLaunchKernelGGL((apply_listed_kernel<MODE, 1, BAGS>), grid2, block, kApplyLdsBytes, stream, dst,
                                (uint64_t)dst_rows, (int)width, p.hdr, p.uniq, p.seg, p.counts, p.perm, (int)n, grads,
                                lr, p.keys_alt, maps, cp);
         HA_LAUNCH_CHECK();
@@ -547,15 +557,20 @@ int apply_by_unique(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, 
     }
     HA_CHECK_HIP(hipMemsetAsync(&p.hdr->reserved[0], 0, sizeof(int64_t), stream));
     if (vec_ok)
-        hipLaunchKernelGGL((apply_unique_kernel<MODE, 4>), grid, block, 0, stream, dst, (uint64_t)dst_rows,
+        hipLaunchKernelGGL((apply_unique_kernel<MODE, 4, BAGS>), grid, block, 0, stream, dst, (uint64_t)dst_rows,
                            (int)width, p.hdr, p.uniq, p.seg, p.counts, p.perm, (int)n, grads, lr, p.keys_alt, maps);
     else
-        hipLaunchKernelGGL((apply_unique_kernel<MODE, 1>), grid, block, 0, stream, dst, (uint64_t)dst_rows,
+        hipLaunchKernelGGL((apply_unique_kernel<MODE, 1, BAGS>), grid, block, 0, stream, dst, (uint64_t)dst_rows,
                            (int)width, p.hdr, p.uniq, p.seg, p.counts, p.perm, (int)n, grads, lr, p.keys_alt, maps);
-    hipLaunchKernelGGL((apply_long_kernel<MODE>), grid, block, kApplyLdsBytes, stream, dst, (uint64_t)dst_rows,
+    hipLaunchKernelGGL((apply_long_kernel<MODE, BAGS>), grid, block, kApplyLdsBytes, stream, dst, (uint64_t)dst_rows,
                        (int)width, p.hdr, p.uniq, p.seg, p.counts, p.perm, (int)n, grads, lr, p.keys_alt, maps);
     HA_LAUNCH_CHECK();
     return 0;
+}
+template <int MODE>
+int apply_by_unique(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, int64_t n,
+                    const float *grads, float lr, hipStream_t stream, ApplyMaps maps) {
+    return apply_by_unique_impl<MODE, false>(dst, dst_rows, width, plan_ws, n, grads, lr, stream, maps);
 }
 template int apply_by_unique<kModeSgd>(float *, int64_t, int64_t, void *, int64_t, const float *, float, hipStream_t, ApplyMaps);
 template int apply_by_unique<kModePush>(float *, int64_t, int64_t, void *, int64_t, const float *, float, hipStream_t, ApplyMaps);
@@ -581,19 +596,58 @@ __global__ __launch_bounds__(1024, 4) void apply_opt_kernel(
 }
 }  // namespace ha
 
-extern "C" int ha_sparse_opt_fused_f32ids(int kind, float *param, int64_t rows, int64_t width, const float *ids,
-                                          int64_t n, const float *grads, float *state1, float *state2,
-                                          const float *hyper_host, void *plan_ws, ha_stream_t stream) {
-    using namespace ha;
-    HA_REQUIRE(kind == kAdaGrad || kind == kAdam || kind == kAdamW, "sparse_opt_fused: kind must be 0 (AdaGrad), "
-               "1 (Adam) or 2 (AdamW)");
-    HA_REQUIRE(n >= 0 && rows >= 0 && width >= 1 && width < (1 << 30), "sparse_opt_fused: bad sizes");
+namespace ha {
+// The same on POOLED gradients (sum-pooled lookup, bagsum.hip): the gradient row of occurrence i is the row of its bag -- i / bag
+// for fixed bags (maps.valdiv, in registers), bag_of[i] for ragged ones (maps.valmap).  Sums and optimizer step are kModeOpt's.
+template <int VEC, bool FIXED>
+__global__ __launch_bounds__(1024, 4) void apply_opt_bags_kernel(
+    float *__restrict__ dst, uint64_t dst_rows, int width, const uint32_t *__restrict__ sorted,
+    const int32_t *__restrict__ perm, int n, const float *__restrict__ bag_grads, ApplyMaps maps) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
+    if (FIXED)
+        maps.valmap = nullptr;
+    else
+        maps.valdiv = 0;
+    apply_body<kModeOpt, VEC, false, kHandNone, true>(dst, dst_rows, width, sorted, perm, nullptr, n, bag_grads, 1.f,
+                                                      blockIdx.x, s_apply, nullptr, maps);
+}
+
+int scratch_get(hipStream_t stream, size_t bytes, void **out);   // capi.hip
+
+// Shared body of ha_sparse_opt_fused_{f32,u64}ids (pooled == false: grads is [n, width]) and ha_sparse_opt_fused_bags_*
+// (pooled: grads is [nbags, width], bags as ha_gather_sum_* describes them).  Every check precedes any device access.
+template <typename IdT>
+static int sparse_opt_fused(const char *what, int kind, float *param, int64_t rows, int64_t width, const IdT *ids, int64_t n,
+                            const float *grads, bool pooled, int64_t bag, const int64_t *offsets, int64_t nbags,
+                            float *state1, float *state2, const float *hyper_host, void *plan_ws, ha_stream_t stream) {
+    HA_REQUIRE(kind == kAdaGrad || kind == kAdam || kind == kAdamW, "%s: kind must be 0 (AdaGrad), 1 (Adam) or 2 (AdamW)", what);
+    HA_REQUIRE(n >= 0 && rows >= 0 && width >= 1 && width < (1 << 30) && n < (1ll << 31), "%s: bad sizes", what);
+    if (pooled) {
+        HA_REQUIRE(nbags >= 0 && bag >= 0 && nbags < (1ll << 31), "%s: bad sizes bag=%ld nbags=%ld", what, (long)bag, (long)nbags);
+        HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld)", what, (long)bag);
+        HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids",
+                   what, (long)n, (long)nbags, (long)bag);
+    }
     if (n == 0)
         return 0;
-    HA_REQUIRE(param && ids && grads && state1 && (kind == kAdaGrad || state2) && hyper_host && plan_ws,
-               "sparse_opt_fused: null pointer");
+    HA_REQUIRE(param && ids && grads && state1 && (kind == kAdaGrad || state2) && hyper_host && plan_ws, "%s: null pointer",
+               what);
+    HA_REQUIRE(!pooled || nbags >= 1, "%s: %ld ids in no bag", what, (long)n);
     hipStream_t s = as_stream(stream);
-    if (ha_plan_sort_f32ids_lim(ids, n, plan_ws, static_cast<uint64_t>(rows), stream))
+    const bool fixed = offsets == nullptr;
+    const int32_t *bag_of = nullptr;
+    if (pooled && !fixed) {      // ragged bags: the bag of every occurrence, in the per-stream scratch
+        void *ws = nullptr;
+        if (scratch_get(s, static_cast<size_t>(n) * 4, &ws))
+            return -1;
+        if (ha_bag_of(offsets, nbags, n, static_cast<int32_t *>(ws), stream))
+            return -1;
+        bag_of = static_cast<const int32_t *>(ws);
+    }
+    if (sizeof(IdT) == 4 ? ha_plan_sort_f32ids_lim(reinterpret_cast<const float *>(ids), n, plan_ws,
+                                                   static_cast<uint64_t>(rows), stream)
+                         : ha_plan_sort_u64ids_lim(reinterpret_cast<const uint64_t *>(ids), n, plan_ws,
+                                                   static_cast<uint64_t>(rows), stream))
         return -1;
     ApplyMaps maps{};
     maps.opt_s1 = state1;
@@ -607,9 +661,15 @@ extern "C" int ha_sparse_opt_fused_f32ids(int kind, float *param, int64_t rows, 
     maps.oa.beta1t = hyper_host[4];
     maps.oa.beta2t = hyper_host[5];
     maps.oa.weight_decay = hyper_host[6];
+    if (pooled) {
+        maps.valmap = bag_of;
+        maps.valdiv = fixed ? static_cast<int>(bag) : 0;
+    }
     if (n > kSmallMax) {
         if (ha_plan_finish(plan_ws, n, stream))
             return -1;
+        if (pooled)
+            return apply_by_unique_impl<kModeOpt, true>(param, rows, width, plan_ws, n, grads, 1.f, s, maps);
         return apply_by_unique<kModeOpt>(param, rows, width, plan_ws, n, grads, 1.f, s, maps);
     }
     PlanPtrs p = plan_layout(plan_ws, n);
@@ -618,7 +678,25 @@ extern "C" int ha_sparse_opt_fused_f32ids(int kind, float *param, int64_t rows, 
                         (reinterpret_cast<uintptr_t>(grads) % 16 == 0) &&
                         (reinterpret_cast<uintptr_t>(state1) % 16 == 0) &&
                         (state2 == nullptr || reinterpret_cast<uintptr_t>(state2) % 16 == 0);
-    if (vec_ok) {
+    if (pooled) {
+        static DeviceOnce lds_allowed;
+        if (lds_allowed.run([]() -> int {
+                HA_ALLOW_LDS((apply_opt_bags_kernel<4, true>), kApplyLdsBytes);
+                HA_ALLOW_LDS((apply_opt_bags_kernel<4, false>), kApplyLdsBytes);
+                HA_ALLOW_LDS((apply_opt_bags_kernel<1, true>), kApplyLdsBytes);
+                HA_ALLOW_LDS((apply_opt_bags_kernel<1, false>), kApplyLdsBytes);
+                return 0;
+            }))
+            return -1;
+#define HA_OPT_BAGS_CASE(V, F)                                                                                           \
+    hipLaunchKernelGGL((apply_opt_bags_kernel<V, F>), dim3(blocks), dim3(1024), kApplyLdsBytes, s, param, (uint64_t)rows, \
+                       (int)width, p.sorted, p.perm, (int)n, grads, maps)
+        if (vec_ok && fixed) HA_OPT_BAGS_CASE(4, true);
+        else if (vec_ok) HA_OPT_BAGS_CASE(4, false);
+        else if (fixed) HA_OPT_BAGS_CASE(1, true);
+        else HA_OPT_BAGS_CASE(1, false);
+#undef HA_OPT_BAGS_CASE
+    } else if (vec_ok) {
         HA_ALLOW_LDS((apply_opt_kernel<4>), kApplyLdsBytes);
         hipLaunchKernelGGL((apply_opt_kernel<4>), dim3(blocks), dim3(1024), kApplyLdsBytes, s, param, (uint64_t)rows,
                            (int)width, p.sorted, p.perm, (int)n, grads, maps);
@@ -629,6 +707,37 @@ extern "C" int ha_sparse_opt_fused_f32ids(int kind, float *param, int64_t rows, 
     }
     HA_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace ha
+
+extern "C" int ha_sparse_opt_fused_f32ids(int kind, float *param, int64_t rows, int64_t width, const float *ids,
+                                          int64_t n, const float *grads, float *state1, float *state2,
+                                          const float *hyper_host, void *plan_ws, ha_stream_t stream) {
+    return ha::sparse_opt_fused<float>("ha_sparse_opt_fused_f32ids", kind, param, rows, width, ids, n, grads, false, 0, nullptr, 0, state1,
+                                       state2, hyper_host, plan_ws, stream);
+}
+
+extern "C" int ha_sparse_opt_fused_u64ids(int kind, float *param, int64_t rows, int64_t width, const uint64_t *ids,
+                                          int64_t n, const float *grads, float *state1, float *state2,
+                                          const float *hyper_host, void *plan_ws, ha_stream_t stream) {
+    return ha::sparse_opt_fused<uint64_t>("ha_sparse_opt_fused_u64ids", kind, param, rows, width, ids, n, grads, false, 0,
+                                          nullptr, 0, state1, state2, hyper_host, plan_ws, stream);
+}
+
+extern "C" int ha_sparse_opt_fused_bags_f32ids(int kind, float *param, int64_t rows, int64_t width, const float *ids,
+                                               int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets,
+                                               int64_t nbags, float *state1, float *state2, const float *hyper_host,
+                                               void *plan_ws, ha_stream_t stream) {
+    return ha::sparse_opt_fused<float>("ha_sparse_opt_fused_bags_f32ids", kind, param, rows, width, ids, n, bag_grads, true, bag,
+                                       offsets, nbags, state1, state2, hyper_host, plan_ws, stream);
+}
+
+extern "C" int ha_sparse_opt_fused_bags_u64ids(int kind, float *param, int64_t rows, int64_t width, const uint64_t *ids,
+                                               int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets,
+                                               int64_t nbags, float *state1, float *state2, const float *hyper_host,
+                                               void *plan_ws, ha_stream_t stream) {
+    return ha::sparse_opt_fused<uint64_t>("ha_sparse_opt_fused_bags_u64ids", kind, param, rows, width, ids, n, bag_grads, true,
+                                          bag, offsets, nbags, state1, state2, hyper_host, plan_ws, stream);
 }
 
 extern "C" int ha_sgd_apply(float *table, int64_t rows, int64_t width,

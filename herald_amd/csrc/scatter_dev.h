@@ -59,6 +59,18 @@ struct ApplyMaps {
 __device__ __forceinline__ int bag_row(int idx, int valdiv) {
     return static_cast<int>(static_cast<uint32_t>(idx) / static_cast<uint32_t>(valdiv));
 }
+// source row of occurrence index idx in the by-unique kernels (scatter.hip): the identity unless BAGS, then through valmap
+// (ragged bags) or valdiv (fixed bags) as the by-position body does
+template <bool BAGS>
+__device__ __forceinline__ int src_row(int idx, const ApplyMaps &maps) {
+    if (BAGS) {
+        if (maps.valmap)
+            idx = maps.valmap[idx];
+        if (maps.valdiv)
+            idx = bag_row(idx, maps.valdiv);
+    }
+    return idx;
+}
 enum : int { kPosMiss = 1, kPosInit = 2, kPosPush = 4, kPosHead = 8, kPosTemp = 16, kPosVictim = 32, kPosVictimHg = 64,
              kPosVictimPush = 128, kPosKeep = 256 };
 

@@ -8,6 +8,8 @@ Mirrors (paths relative to /root/reference):
   ParameterServerCommunicateOp                    python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
   ParameterServerSparsePullOp                     python/hetu/gpu_ops/ParameterServerCommunicate.py:254-306
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
+  Momentum / AdaGrad / Adam / AdamW sparse dispatch  python/hetu/gpu_links/OptimizerLink.py:37-100 (*_update_sparse: fused, and
+                                                  straight from the pooled gradient of EmbeddingLookUpSum_Gradient)
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
 cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and two switches of this build: cache_plan_ahead (the cache's
@@ -178,7 +180,7 @@ class EmbeddingLookUpSum_Gradient:
             return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
                                      bag=index.shape[1])
         return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
-                                 bag_of=ops.bag_of(offsets, index.numel()))
+                                 bag_of=ops.bag_of(offsets, index.numel()), offsets=offsets)
 
 
 def sgd_update_sparse(param, grad, lr, stream=None):
@@ -198,6 +200,112 @@ def sgd_update_sparse(param, grad, lr, stream=None):
     ops.dl_call("SGDOptimizerSparseUpdate",
                 [param.table, grad.indices.contiguous(), grad.values.reshape(-1, param.table.shape[1]).contiguous()],
                 scalars=[ctypes.c_float(lr)], stream=stream)
+
+
+# ---- the sparse branches of the other optimizers (OptimizerLink.py:37-100), on a device table ----------------------------
+def _sparse_args(name, param, grad, states):
+    """Shape checks shared by the *_update_sparse functions below (no native call is made before they pass).  Returns
+    (table, width)."""
+    table = param.table
+    if table is None or table.dim() != 2:
+        raise ValueError("%s: the parameter must hold a 2-D device table" % name)
+    width = table.shape[1]
+    for what, st in states:
+        if st is None or tuple(st.shape) != tuple(table.shape) or st.dtype != table.dtype:
+            raise ValueError("%s: %s must be a float32 tensor of the table's shape %s" % (name, what, tuple(table.shape)))
+    if grad.indices is None or grad.values is None:
+        raise ValueError("%s: the gradient has no indices / values" % name)
+    if grad.values.dim() < 1 or grad.values.shape[-1] != width:
+        raise ValueError("%s: gradient rows must be %d wide, got %s" % (name, width, tuple(grad.values.shape)))
+    n = grad.indices.numel()
+    nrows = grad.values.numel() // width
+    if not getattr(grad, "pooled", False):
+        if nrows != n:
+            raise ValueError("%s: %d gradient rows for %d indices" % (name, nrows, n))
+    elif grad.bag is not None:
+        if int(grad.bag) < 1 or n != nrows * int(grad.bag):
+            raise ValueError("%s: %d indices are not %d bags of %s ids" % (name, n, nrows, grad.bag))
+    else:
+        if grad.bag_of.numel() != n:
+            raise ValueError("%s: bag_of must have one entry per index" % name)
+        if grad.offsets is not None and grad.offsets.numel() != nrows + 1:
+            raise ValueError("%s: offsets must have one entry per gradient row and one more" % name)
+    return table, width
+
+
+def _reference_slices(grad, width, dedup, stream):
+    """The reference's own sequence on a copy of the slices: reduce_sum's broadcast gradient (expanded_values), then
+    IndexedSlices.deduplicate for the optimizers that ask for it.  Returns (indices [m], values [m, width])."""
+    ref = ops.IndexedSlices(indices=grad.indices.reshape(-1).contiguous(), values=grad.expanded_values(stream),
+                            dense_shape=grad.dense_shape)
+    if dedup:
+        ref.deduplicate(stream)
+    return ref.indices.reshape(-1).contiguous(), ref.values.reshape(-1, width).contiguous()
+
+
+def _bag_call_args(name, grad, width):
+    """(ids, offsets, values) as the one-call bag optimizers of ops take them."""
+    values = grad.values.reshape(-1, width).contiguous()
+    if grad.bag is not None:
+        return grad.indices.reshape(-1, int(grad.bag)).contiguous(), None, values
+    if grad.offsets is None:
+        raise ValueError("%s: ragged pooled slices need their offsets (EmbeddingLookUpSum_Gradient attaches them); "
+                         "fuse_bags=False takes bag_of alone" % name)
+    return grad.indices.reshape(-1).contiguous(), grad.offsets, values
+
+
+def momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream=None, fuse_bags=True):
+    """momentum_update's sparse branch (OptimizerLink.py:37-49): MomentumOptimizerSparseUpdate WITHOUT deduplication.
+    Pooled slices go to ops.momentum_sparse_update_bags -- no expanded gradient is built; fuse_bags=False runs the reference's
+    sequence (expanded_values, then the symbol): the same bits."""
+    table, width = _sparse_args("momentum_update_sparse", param, grad, [("velocity", velocity)])
+    if fuse_bags and getattr(grad, "pooled", False):
+        ids, offsets, values = _bag_call_args("momentum_update_sparse", grad, width)
+        ops.momentum_sparse_update_bags(table, ids, values, velocity, lr, momentum, nesterov, offsets=offsets, stream=stream)
+        return
+    ids, values = _reference_slices(grad, width, False, stream)
+    ops.dl_call("MomentumOptimizerSparseUpdate", [table, ids, values, velocity],
+                scalars=[ctypes.c_float(lr), ctypes.c_float(momentum), ctypes.c_bool(bool(nesterov))], stream=stream)
+
+
+def _fused_update_sparse(name, kind, symbol, param, grad, state1, state2, hyper, scalars, stream, fuse_bags):
+    states = [("the first state", state1)] + ([("the second state", state2)] if kind != "adagrad" else [])
+    table, width = _sparse_args(name, param, grad, states)
+    if not fuse_bags:        # the reference: deduplicate (on the expanded gradient), then the symbol on the reduced slices
+        ids, values = _reference_slices(grad, width, True, stream)
+        arrays = [table, ids, values, state1] + ([state2] if kind != "adagrad" else [])
+        ops.dl_call(symbol, arrays, scalars=[ctypes.c_float(x) for x in scalars], stream=stream)
+        return
+    if getattr(grad, "pooled", False):
+        ids, offsets, values = _bag_call_args(name, grad, width)
+        ops.sparse_opt_fused_bags(kind, table, ids, values, state1, state2, offsets=offsets, stream=stream, **hyper)
+        return
+    ops.sparse_opt_fused(kind, table, grad.indices.reshape(-1).contiguous(), grad.values.reshape(-1, width).contiguous(),
+                         state1, state2, stream=stream, **hyper)
+
+
+def adagrad_update_sparse(param, grad, accumulation, lr, eps, stream=None, fuse_bags=True):
+    """adagrad_update's sparse branch (OptimizerLink.py:52-66): grad.deduplicate + AdaGradOptimizerSparseUpdate, as ONE fused
+    call on the raw ids (ops.sparse_opt_fused) -- for pooled slices on the pooled gradient (ops.sparse_opt_fused_bags).
+    fuse_bags=False: the reference's own sequence (expanded_values, deduplicate, the symbol); the same bits."""
+    _fused_update_sparse("adagrad_update_sparse", "adagrad", "AdaGradOptimizerSparseUpdate", param, grad, accumulation, None,
+                         dict(lr=lr, eps=eps), [lr, eps], stream, fuse_bags)
+
+
+def adam_update_sparse(param, grad, expavg, expavgsq, lr, beta1, beta2, beta1t, beta2t, eps, stream=None, fuse_bags=True):
+    """adam_update's sparse branch (OptimizerLink.py:69-84), fused as adagrad_update_sparse is."""
+    _fused_update_sparse("adam_update_sparse", "adam", "AdamOptimizerSparseUpdate", param, grad, expavg, expavgsq,
+                         dict(lr=lr, eps=eps, beta1=beta1, beta2=beta2, beta1t=beta1t, beta2t=beta2t),
+                         [lr, beta1, beta2, beta1t, beta2t, eps], stream, fuse_bags)
+
+
+def adamw_update_sparse(param, grad, expavg, expavgsq, lr, beta1, beta2, beta1t, beta2t, eps, weight_decay, stream=None,
+                        fuse_bags=True):
+    """adamw_update's sparse branch (OptimizerLink.py:86-100), fused as adagrad_update_sparse is."""
+    _fused_update_sparse("adamw_update_sparse", "adamw", "AdamWOptimizerSparseUpdate", param, grad, expavg, expavgsq,
+                         dict(lr=lr, eps=eps, beta1=beta1, beta2=beta2, beta1t=beta1t, beta2t=beta2t,
+                              weight_decay=weight_decay),
+                         [lr, beta1, beta2, beta1t, beta2t, eps, weight_decay], stream, fuse_bags)
 
 
 class ParameterServerCommunicateOp:

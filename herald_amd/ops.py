@@ -449,21 +449,89 @@ def sgd_apply_finish(table, plan, grads, lr, stream=None, next_ids=None):
 _OPT_KINDS = {"adagrad": 0, "adam": 1, "adamw": 2}
 
 
+def _opt_args(kind, param, state1, state2):
+    """The argument checks of sparse_opt_fused_bags (sparse_opt_fused keeps the checks it always had: the native call's);
+    returns the native kind."""
+    if kind not in _OPT_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(_OPT_KINDS), kind))
+    _require(param, torch.float32, "param")
+    if param.dim() != 2:
+        raise ValueError("param must be 2-D")
+    _require(state1, torch.float32, "state1")
+    if state1.numel() != param.numel():
+        raise ValueError("state1 must have the size of param")
+    if kind != "adagrad" and state2 is None:
+        raise ValueError("%s needs state2 (exp_avg_sq)" % kind)
+    if state2 is not None:      # (AdaGrad leaves a given state2 as it is)
+        _require(state2, torch.float32, "state2")
+        if state2.numel() != param.numel():
+            raise ValueError("state2 must have the size of param")
+    return _OPT_KINDS[kind]
+
+
 def sparse_opt_fused(kind, param, ids, grads, state1, state2=None, lr=0.01, eps=1e-7, beta1=0.9, beta2=0.999,
                      beta1t=0.9, beta2t=0.999, weight_decay=0.0, plan=None, stream=None):
     """grad.deduplicate() + {AdaGrad,Adam,AdamW}OptimizerSparseUpdate (OptimizerLink.py:52-100) in one call on
-    the RAW (not deduplicated) float32 ids and their gradient rows; bit-identical to the two-step sequence."""
+    the RAW (not deduplicated) ids -- float32 or (u)int64 -- and their gradient rows; bit-identical to the two-step
+    sequence."""
+    L = _lib.load()
     _require(param, torch.float32, "param")
-    _require(ids, torch.float32, "ids")
+    fn = _ids_fn(ids, L.ha_sparse_opt_fused_f32ids, L.ha_sparse_opt_fused_u64ids)
+    _require(ids, ids.dtype, "ids")
     _require(grads, torch.float32, "grads")
     n = ids.numel()
     if plan is None:
         plan = IndexPlan(max(n, 1), param.device)
     hyper = (ctypes.c_float * 7)(lr, eps, beta1, beta2, beta1t, beta2t, weight_decay)
-    check(_lib.load().ha_sparse_opt_fused_f32ids(_OPT_KINDS[kind], _ptr(param), param.shape[0], param.shape[1],
-                                                 _ptr(ids), n, _ptr(grads), _ptr(state1),
-                                                 _ptr(state2) if state2 is not None else None, hyper, _ptr(plan.ws),
-                                                 _stream_ptr(stream)), "ha_sparse_opt_fused_f32ids")
+    check(fn(_OPT_KINDS[kind], _ptr(param), param.shape[0], param.shape[1], _ptr(ids), n, _ptr(grads), _ptr(state1),
+             _ptr(state2) if state2 is not None else None, hyper, _ptr(plan.ws), _stream_ptr(stream)),
+          "ha_sparse_opt_fused")
+    return param
+
+
+def sparse_opt_fused_bags(kind, param, ids, bag_grads, state1, state2=None, offsets=None, lr=0.01, eps=1e-7, beta1=0.9,
+                          beta2=0.999, beta1t=0.9, beta2t=0.999, weight_decay=0.0, plan=None, stream=None):
+    """sparse_opt_fused on the POOLED gradient of a sum-pooled lookup: ids [B, F] (fixed bags), or ids [n] with offsets int64
+    [B + 1] (ragged bags), bag_grads [B, width] -- occurrence i takes the row of its bag and no [n, width] gradient is built.
+    Bit for bit sparse_opt_fused on the expanded gradient, in param and both states."""
+    L = _lib.load()
+    k = _opt_args(kind, param, state1, state2)
+    _require(bag_grads, torch.float32, "bag_grads")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    if bag_grads.numel() != nbags * param.shape[1]:
+        raise ValueError("bag_grads must be [B, width]")
+    fn = getattr(L, "ha_sparse_opt_fused_bags_" + _ids_fn(ids, "f32ids", "u64ids"))
+    if plan is None:
+        plan = IndexPlan(max(n, 1), param.device)
+    elif plan.capacity < n:
+        raise ValueError("plan capacity %d < %d ids" % (plan.capacity, n))
+    hyper = (ctypes.c_float * 7)(lr, eps, beta1, beta2, beta1t, beta2t, weight_decay)
+    check(fn(k, _ptr(param), param.shape[0], param.shape[1], _ptr(ids), n, _ptr(bag_grads), bag,
+             _ptr(offsets) if offsets is not None else None, nbags, _ptr(state1),
+             _ptr(state2) if state2 is not None else None, hyper, _ptr(plan.ws), _stream_ptr(stream)),
+          "ha_sparse_opt_fused_bags")
+    return param
+
+
+def momentum_sparse_update_bags(param, ids, bag_grads, velocity, lr, momentum, nesterov=False, offsets=None, stream=None):
+    """MomentumOptimizerSparseUpdate (OptimizerLink.py:37-49: no dedup, duplicates in occurrence order, then the dense
+    phase over the whole table) from the POOLED gradient: ids / offsets / bag_grads as in sparse_opt_fused_bags.  Bit for
+    bit the symbol on the expanded gradient."""
+    L = _lib.load()
+    _require(param, torch.float32, "param")
+    if param.dim() != 2:
+        raise ValueError("param must be 2-D")
+    _require(velocity, torch.float32, "velocity")
+    if velocity.numel() != param.numel():
+        raise ValueError("velocity must have the size of param")
+    _require(bag_grads, torch.float32, "bag_grads")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    if bag_grads.numel() != nbags * param.shape[1]:
+        raise ValueError("bag_grads must be [B, width]")
+    fn = getattr(L, "ha_momentum_sparse_update_bags_" + _ids_fn(ids, "f32ids", "u64ids"))
+    check(fn(_ptr(param), param.shape[0], param.shape[1], _ptr(ids), n, _ptr(bag_grads), bag,
+             _ptr(offsets) if offsets is not None else None, nbags, _ptr(velocity), ctypes.c_float(lr),
+             ctypes.c_float(momentum), 1 if nesterov else 0, _stream_ptr(stream)), "ha_momentum_sparse_update_bags")
     return param
 
 
@@ -1418,12 +1486,16 @@ class IndexedSlices:
     exactly what the reference computes with np.unique + DeduplicateIndexedSlices / cpu_deduplicate.
     """
 
-    def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None):
+    def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None, offsets=None):
         """bag / bag_of (optional): POOLED slices, the gradient of a sum-pooled lookup -- values is [B, width], one row per
         bag, and occurrence i of indices takes the row of its bag: i // bag (fixed bags of `bag` ids) or bag_of[i] (int32 [n],
-        ragged bags)."""
+        ragged bags).  offsets (optional, with bag_of): the int64 [B + 1] offsets bag_of was built from -- what the one-call
+        bag optimizers take (hetu_ops.*_update_sparse)."""
         if bag is not None and bag_of is not None:
             raise ValueError("give at most one of bag and bag_of")
+        if offsets is not None and bag_of is None:
+            raise ValueError("offsets come with bag_of (ragged bags)")
+        self.offsets = offsets
         self.indices = indices
         self.values = values
         self.dense_shape = dense_shape
@@ -1455,10 +1527,10 @@ class IndexedSlices:
     def get_sparse_shape(self):
         return tuple(self.values.shape)
 
-    def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None):
+    def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None, offsets=None):
         self.indices = indices
         self.push_indices = push_indices
-        self.bag, self.bag_of = bag, bag_of
+        self.bag, self.bag_of, self.offsets = bag, bag_of, offsets
         self.values = values
         if self.dense_shape is not None:
             assert tuple(self.dense_shape) == tuple(dense_shape)

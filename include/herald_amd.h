@@ -368,6 +368,30 @@ int ha_apply_mapped2(float *dst, int64_t dst_rows, float *dst2, int64_t width,
 int ha_sparse_opt_fused_f32ids(int kind, float *param, int64_t rows, int64_t width, const float *ids,
                                int64_t n, const float *grads, float *state1, float *state2,
                                const float *hyper_host, void *plan_ws, ha_stream_t stream);
+/* The same for uint64 keys (the plan is ha_plan_sort_u64ids_lim's): equal ids give equal bits. */
+int ha_sparse_opt_fused_u64ids(int kind, float *param, int64_t rows, int64_t width, const uint64_t *ids,
+                               int64_t n, const float *grads, float *state1, float *state2,
+                               const float *hyper_host, void *plan_ws, ha_stream_t stream);
+/* The same on the POOLED gradient of a sum-pooled lookup (ha_gather_sum_*, below): bag_grads is [nbags, width] and
+ * occurrence i takes the row of its bag -- i / bag for fixed bags (bag >= 1, offsets NULL, n == nbags * bag; computed in
+ * registers, no map is read), the bag that offsets places it in for ragged ones (bag == 0, device offsets[nbags + 1];
+ * ha_bag_of builds the map in the per-stream scratch).  No [n, width] gradient exists anywhere: the launch reads
+ * nbags * width * 4 distinct gradient bytes.  kind, state1 / state2, hyper_host and plan_ws are ha_sparse_opt_fused_f32ids'.
+ * Bit for bit, in param, state1 and state2, what ha_sparse_opt_fused_f32ids gives on bag_grads expanded to [n, width],
+ * for every n (one wave per sorted position up to 36,864 ids, waves mapped to unique keys beyond) and in every tolerance
+ * mode (the optimizer step is exact in all of them).  Rows no in-range id names are untouched, an id >= rows is skipped,
+ * n == 0 returns 0 and touches nothing.  width % 4 == 0 with 16-byte aligned param, bag_grads and states takes the
+ * 16-byte path, anything else the scalar one.  Returns -1 before any device access for a kind outside 0..2, a null
+ * pointer, width < 1, a negative size, n >= 2^31, both or neither of bag / offsets, n != nbags * bag, or a missing
+ * state2 for Adam / AdamW. */
+int ha_sparse_opt_fused_bags_f32ids(int kind, float *param, int64_t rows, int64_t width, const float *ids,
+                                    int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets,
+                                    int64_t nbags, float *state1, float *state2, const float *hyper_host,
+                                    void *plan_ws, ha_stream_t stream);
+int ha_sparse_opt_fused_bags_u64ids(int kind, float *param, int64_t rows, int64_t width, const uint64_t *ids,
+                                    int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets,
+                                    int64_t nbags, float *state1, float *state2, const float *hyper_host,
+                                    void *plan_ws, ha_stream_t stream);
 
 /* ---- fused launches (two per training step) --------------------------------
  * ha_lookup_sort_*    == ha_gather_* + ha_plan_sort_*   in ONE launch (forward: the lookup of a
@@ -1245,6 +1269,17 @@ int ha_sgd_sparse_update_bags_f32ids(float *table, int64_t rows, int64_t width, 
 int ha_sgd_sparse_update_bags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n,
                                      const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags, float lr,
                                      ha_stream_t stream);
+/* Momentum / Nesterov from the pooled gradient, one call on an internal per-stream workspace: plan, (ha_bag_of,)
+ * ha_sgd_apply_bags on velocity -- and on param too for Nesterov --, then the dense phase of MomentumOptimizerSparseUpdate
+ * over the whole table (it runs for n == 0 as well, as there).  Bit for bit MomentumOptimizerSparseUpdate on bag_grads
+ * expanded to [n, width]; the tolerance mode is honoured exactly as that symbol honours it.  nesterov: 0 / 1.  Argument
+ * checks as ha_sgd_sparse_update_bags_*, before any device access. */
+int ha_momentum_sparse_update_bags_f32ids(float *param, int64_t rows, int64_t width, const float *ids, int64_t n,
+                                          const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                          float *velocity, float lr, float momentum, int nesterov, ha_stream_t stream);
+int ha_momentum_sparse_update_bags_u64ids(float *param, int64_t rows, int64_t width, const uint64_t *ids, int64_t n,
+                                          const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                          float *velocity, float lr, float momentum, int nesterov, ha_stream_t stream);
 /* Measurement aid (tools/bag_bench.py): column-slice width of ha_gather_sum_*'s 16-byte path, 64 / 128 / 256 floats per
  * wave; 0 = chosen from the batch (the default).  Process-wide; results do not depend on it. */
 int ha_debug_bag_slice(int floats);
