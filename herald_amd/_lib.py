@@ -191,6 +191,7 @@ def _declare(L):
         "ha_shard_steps": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, f32, vp],
         "ha_qapply_steps_sync": [vp, i64, i64, f32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "ha_qapply_steps_counts": [vp, i64, i64, f32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "ha_qapply_geometry": [i64, i64, i64, i64, i64, vp, vp],
         "ha_qapply_sync": [vp, i64, i64, vp, i64, vp, f32, vp, i64, vp, vp, i64, i64, c.c_uint32, vp, vp, vp],
         "ha_xchg_available": [],
         "ha_xchg_unique_id": [vp],

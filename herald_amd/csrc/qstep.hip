@@ -76,6 +76,13 @@ constexpr int kQWpw = kQWg / 64;               // waves (= wave items) per workg
 constexpr int kQCoopSlots = QV_COOPSLOTS;      // workgroups reserved for G items (they loop if there are more)
 constexpr int kQWorkerMax = 448 * 16 / kQWpw;  // worker workgroups: with the coop slots the launch stays below the
                                                // chip's 8,192 resident waves; the waves loop beyond that
+// QV_DEAL = 1 (the product): the wave items of a launch that does not come from the wide path are DEALT over its worker
+// workgroups -- wave wv of worker b takes the items (r * kQWpw + wv) * nworker + b, r = 0, 1, ... -- so that every workgroup
+// holds items from all over the list, which is ordered by class (L, then M, then S).  QV_DEAL = 0: worker b takes the sixteen
+// items from b * kQWpw, and the workgroups at the head of the launch are all L items and copies.
+#ifndef QV_DEAL
+#define QV_DEAL 1
+#endif
 constexpr int kQSmallC = 3, kQSmallM = 16, kQMediumC = 15, kQLongC = 64;
 enum QKind { kQS = 0, kQM = 1, kQL = 2, kQZ = 3, kQG = 4, kQNone = 15 };
 
@@ -184,6 +191,7 @@ struct QArgs {
     int n_g;
     float *out;
     int ncoop, nworker;
+    int deal;       // the wave items are dealt over the workers (q_first_item)
     uint32_t epoch;            // 0: no check; else the tag queue `qh` must carry before an item is read
     uint32_t *err;             // pinned host word raised (8) when the queue never became ready (may be NULL)
     unsigned long long *dbg;   // tools/qstep_timeline.py: {start, end, role | xcc << 8, item kind} per wave
@@ -1452,6 +1460,11 @@ __device__ __forceinline__ void q_coop(const QArgs &a, const QItem &it, float *s
 }
 
 // ---- the three launches ----------------------------------------------------------------------------------------
+// The first item (or pair of items) of wave wv of worker workgroup b; its next ones follow kQWpw * nworker apart.
+__device__ __forceinline__ uint32_t q_first_item(const QArgs &a, int b, uint32_t wv) {
+    return a.deal ? wv * static_cast<uint32_t>(a.nworker) + static_cast<uint32_t>(b)
+                  : static_cast<uint32_t>(b) * static_cast<uint32_t>(kQWpw) + wv;
+}
 // The items of one step: workgroups [0, ncoop) take the G items, the others one wave item per wave.
 static_assert(kQWg == 256 || kQWg == 512 || kQWg == 1024, "workgroups of 4, 8 or 16 waves");
 static_assert(!QV_GOLD || kQWg == 1024, "the sixteen-wave G item needs 1024-thread workgroups");
@@ -1525,7 +1538,7 @@ __global__ __launch_bounds__(kQWg, 8) void qapply_kernel(const QArgs a) {
             // narrow rows: every wave takes a PAIR of consecutive items; two S / Z items share the wave (q_small_pair),
             // anything else is done one after the other
             const uint32_t n1 = n - n0, both = 2u * (n0 < n1 ? n0 : n1), npair = (n + 1u) / 2u;
-            for (uint32_t pe = static_cast<uint32_t>(b) * static_cast<uint32_t>(kQWpw) + wv; pe < npair; pe += stride) {
+            for (uint32_t pe = q_first_item(a, b, wv); pe < npair; pe += stride) {
                 const QEntry *src[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -1557,9 +1570,10 @@ __global__ __launch_bounds__(kQWg, 8) void qapply_kernel(const QArgs a) {
                 }
             }
         } else
-        for (uint32_t e = static_cast<uint32_t>(b) * static_cast<uint32_t>(kQWpw) + wv; e < n; e += stride) {
+        for (uint32_t e = q_first_item(a, b, wv); e < n; e += stride) {
 #if QV_INTERLEAVE
-            // Wave items and copy items ALTERNATE over the launch while both last (then the rest of the longer list):
+            // Wave items and copy items ALTERNATE over the launch while both last (then the rest of the longer list; dealt,
+            // a workgroup's waves are nworker items apart: the host keeps nworker ODD, so they alternate inside it too):
             // a copy writes m rows for one it reads, an apply item reads more than it writes, and a compute unit that
             // holds only one kind is bound by its load or its store path while the other idles.  With all copies at the
             // end of the launch a step takes 13.5 us, alternating 12.4 (same box; copies first 13.5, two copies per wave
@@ -1602,7 +1616,7 @@ __global__ __launch_bounds__(kQWg, 8) void qapply_kernel(const QArgs a) {
                     src = a.qcoop + blockIdx.x;
                 } else if (a.width > 128) {
                     const uint32_t n0 = min(a.qh->n_wave, a.cap_wave), n = n0 + min(a.qh->n_copy, a.cap_copy);
-                    const uint32_t e = static_cast<uint32_t>(b) * static_cast<uint32_t>(kQWpw) + static_cast<uint32_t>(threadIdx.x >> 6);
+                    const uint32_t e = q_first_item(a, b, static_cast<uint32_t>(threadIdx.x >> 6));
                     const uint32_t n1 = n - n0, both = 2u * (n0 < n1 ? n0 : n1);
                     if (e < n)
                         src = e < both ? ((e & 1u) ? a.qcopy + (e >> 1) : a.qwave + (e >> 1))
@@ -1813,7 +1827,7 @@ static int qapply_lists(float *table, int64_t rows, int64_t width, const int32_t
                         float lr, const int32_t *perm_next, int64_t n_next, float *next_out, const void *queue_cur,
                         int64_t queue_n_cap, int64_t n_max, hipStream_t stream, unsigned long long *dbg = nullptr,
                         int64_t wave_items = -1, uint32_t epoch = 0, uint32_t *err = nullptr, hipEvent_t done = nullptr,
-                        int64_t coop_items = -1);
+                        int64_t coop_items = -1, bool deal = QV_DEAL != 0);
 
 static int qapply(float *table, int64_t rows, int64_t width, void *plan_cur, int64_t n_cur, const float *grads, float lr,
                   void *plan_next, int64_t n_next, float *next_out, const void *queue_cur, int64_t queue_n_cap,
@@ -1826,12 +1840,34 @@ static int qapply(float *table, int64_t rows, int64_t width, void *plan_cur, int
                         kQMax, stream, dbg, wave_items, epoch, err, done);
 }
 
+// The grid of one apply launch: workgroups [0, ncoop) for the G items, nworker workgroups for the wave items (hints < 0: unknown).
+static void qapply_geometry(int64_t width, int64_t n_cur, int64_t n_next, int64_t wave_items, int64_t coop_items, bool deal,
+                            int &ncoop, int &nworker) {
+    ncoop = n_cur >= kQLongC ? kQCoopSlots : 0;
+    if (coop_items >= 0) {      // the caller knows the number of workgroup items (wide batches have thousands): one workgroup
+        const int64_t most = 4096 / kQWpw;      // each, up to half of the chip's resident waves
+        ncoop = static_cast<int>(coop_items < most ? coop_items : most);
+    }
+    // wave items <= ceil(width/512) * (n_cur + n_next); beyond kQWorkerMax workgroups the waves loop
+    const int64_t bound = static_cast<int64_t>(ceil_div(width, 512)) * (n_cur + n_next);
+    nworker = static_cast<int>(bound / kQWpw + 1 < kQWorkerMax ? bound / kQWpw + 1 : kQWorkerMax);
+    // the caller knows how many wave items the queue holds (ha_qstep_queue_mirror): no workgroups that find nothing --
+    // a shorter launch ramp, and free slots for the preparation launches that run beside the steps
+    if (wave_items >= 0 && wave_items / kQWpw + 1 < nworker)
+        nworker = static_cast<int>(wave_items / kQWpw + 1);
+    // dealt, nworker is ODD: along the waves of a workgroup the item index advances by nworker, and its parity picks apply or
+    // copy (QV_INTERLEAVE) -- an even nworker makes workgroups of one kind only (13.5 us per step against 12.3,
+    // docs/EXPERIMENTS.md round 3).  One more workgroup where the cap allows, else one fewer: the waves loop anyway.
+    if (deal && (nworker & 1) == 0)
+        nworker += nworker < kQWorkerMax ? 1 : -1;
+}
+
 // perm_cur / perm_next: the occurrence lists of the batch to apply / the destination lists of the batch to look up (what
 // the items' `st` / `fs` index); n_max: the largest batch of the path that built the queue
 static int qapply_lists(float *table, int64_t rows, int64_t width, const int32_t *perm_cur, int64_t n_cur, const float *grads,
                         float lr, const int32_t *perm_next, int64_t n_next, float *next_out, const void *queue_cur,
                         int64_t queue_n_cap, int64_t n_max, hipStream_t stream, unsigned long long *dbg,
-                        int64_t wave_items, uint32_t epoch, uint32_t *err, hipEvent_t done, int64_t coop_items) {
+                        int64_t wave_items, uint32_t epoch, uint32_t *err, hipEvent_t done, int64_t coop_items, bool deal) {
     HA_REQUIRE(table != nullptr && rows >= 0 && rows <= 0xFFFFFFFEll && width >= 4 && width % 4 == 0 &&
                    width <= (1 << 20) && reinterpret_cast<uintptr_t>(table) % 16 == 0,
                "ha_qapply: the table must be 16-byte aligned with rows of a multiple of 4 floats");
@@ -1873,18 +1909,8 @@ static int qapply_lists(float *table, int64_t rows, int64_t width, const int32_t
     a.perm_g = perm_next;
     a.n_g = static_cast<int>(n_next);
     a.out = next_out;
-    a.ncoop = n_cur >= kQLongC ? kQCoopSlots : 0;
-    if (coop_items >= 0) {      // the caller knows the number of workgroup items (wide batches have thousands): one workgroup
-        const int64_t most = 4096 / kQWpw;      // each, up to half of the chip's resident waves
-        a.ncoop = static_cast<int>(coop_items < most ? coop_items : most);
-    }
-    // wave items <= ceil(width/512) * (n_cur + n_next); beyond kQWorkerMax workgroups the waves loop
-    const int64_t bound = static_cast<int64_t>(ceil_div(width, 512)) * (n_cur + n_next);
-    a.nworker = static_cast<int>(bound / kQWpw + 1 < kQWorkerMax ? bound / kQWpw + 1 : kQWorkerMax);
-    // the caller knows how many wave items the queue holds (ha_qstep_queue_mirror): no workgroups that find nothing --
-    // a shorter launch ramp, and free slots for the preparation launches that run beside the steps
-    if (wave_items >= 0 && wave_items / kQWpw + 1 < a.nworker)
-        a.nworker = static_cast<int>(wave_items / kQWpw + 1);
+    a.deal = deal ? 1 : 0;
+    qapply_geometry(width, n_cur, n_next, wave_items, coop_items, deal, a.ncoop, a.nworker);
     // (sync = "flags": a launch whose queue is still being built POLLS -- workgroup 0 the epoch words, the others its verdict --
     // and while it does, no compute unit is EMPTY; the builder's workgroups fit only an empty one: 106 scalar registers a wave,
     // beside a workgroup of this kernel a SIMD's scalar file is short.  A builder that has not started by then starts when the
@@ -2483,6 +2509,15 @@ extern "C" int ha_qapply_steps_counts(float *table, int64_t rows, int64_t width,
     return ha_qapply_steps_sync(table, rows, width, lr, queue_n_cap, count, plan_cur, n_cur, grads, plan_next, n_next, next_out,
                                 queue_cur, wave_items, epochs, err, done_event, stream);
 }
+extern "C" int ha_qapply_geometry(int64_t width, int64_t n_cur, int64_t n_next, int64_t wave_items, int64_t coop_items,
+                                  int32_t *ncoop, int32_t *nworker) {
+    HA_REQUIRE(ncoop && nworker && width >= 4 && n_cur >= 0 && n_next >= 0, "ha_qapply_geometry: bad arguments");
+    int c = 0, w = 0;
+    qapply_geometry(width, n_cur, n_next, wave_items, coop_items, QV_DEAL != 0, c, w);
+    *ncoop = c;
+    *nworker = w;
+    return 0;
+}
 extern "C" int ha_qapply_sync(float *table, int64_t rows, int64_t width, void *plan_cur, int64_t n_cur, const float *grads,
                               float lr, void *plan_next, int64_t n_next, float *next_out, const void *queue_cur,
                               int64_t queue_n_cap, int64_t wave_items, uint32_t epoch, uint32_t *err, void *done_event,
@@ -2580,7 +2615,9 @@ extern "C" int ha_qbig_apply(float *table, int64_t rows, int64_t width, void *ws
     if (n_next > 0)
         qbig_layout(ws_next, n_cap, &g);
     return qapply_lists(table, rows, width, a.gperm, n_cur, grads, lr, g.gperm, n_next, next_out, queue_cur, n_cap, kQBigMax,
-                        as_stream(stream), nullptr, -1, epoch, err, static_cast<hipEvent_t>(done_event), coop_items);
+                        as_stream(stream), nullptr, -1, epoch, err, static_cast<hipEvent_t>(done_event), coop_items,
+                        false);     // (a wide launch loops several times beside up to 256 G workgroups: dealt it measured
+                                    // 48.3 us per step against 47.6 at bs 4096 d 128, docs/EXPERIMENTS.md round 7)
 }
 // a wide plan's per-bucket results for tests: bucket offsets [P + 1], then per bucket its number of unique keys
 extern "C" int ha_qbig_plan_view(void *ws, int64_t n_cap, void **boff, void **bhdr, void **uniq, void **counts, void **seg,

@@ -1458,6 +1458,15 @@ class QueueStepPipeline:
         return self._call(self.c, grads, ahead_ids, out, stream)
 
 
+def qapply_geometry(width, n_cur, n_next, wave_items=-1, coop_items=-1):
+    """(G workgroups, worker workgroups) of the apply launch of a step with these batch sizes and launch-size hints on the
+    current device (-1: no hint)."""
+    nc, nw = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(_lib.load().ha_qapply_geometry(width, n_cur, n_next, wave_items, coop_items, ctypes.byref(nc), ctypes.byref(nw)),
+          "ha_qapply_geometry")
+    return nc.value, nw.value
+
+
 def push_apply_finish(table, plan, grads, stream=None):
     _require(table, torch.float32, "table")
     _require(grads, torch.float32, "grads")

@@ -621,6 +621,13 @@ int ha_qapply_steps_counts(float *table, int64_t rows, int64_t width, float lr, 
                            const int64_t *wave_items, const uint32_t *const *counts_host, const uint32_t *epochs, uint32_t *err,
                            void *done_event, ha_stream_t stream);
 
+/* The grid of the apply launch of a step (ha_qapply*) with these batch sizes and launch-size hints (< 0: none), for tests and
+ * tools: workgroups [0, ncoop) take the G items, the nworker behind them the wave items -- DEALT: wave wv of worker b takes the
+ * items (r * 16 + wv) * nworker + b, r = 0, 1, ...; nworker is odd so that apply and copy items, which alternate over the
+ * list, alternate inside every workgroup too.  (ha_qbig_apply keeps worker b on the sixteen items from 16 * b.) */
+int ha_qapply_geometry(int64_t width, int64_t n_cur, int64_t n_next, int64_t wave_items, int64_t coop_items, int32_t *ncoop,
+                       int32_t *nworker);
+
 /* The row / key exchange of the sharded sparse pull and push as RCCL point-to-point calls made by the LIBRARY on the caller's
  * stream (the reference's worker sends and receives inside C++ too: PSAgent::vecPullSparse / vecPushSparse,
  * ps-lite/include/ps/worker/PSAgent.h:124-237 -- U_s keys and U_s x d floats per server, ps/psf/sparse.h:9-32): one

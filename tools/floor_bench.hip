@@ -4,6 +4,9 @@
 //              row back and M output rows (streamed) -- the step's real traffic (42.7 MB at W = 6000, C = 1.1, M = 1.1)
 //              WITHOUT any metadata chain (addresses from the wave number).  ipw = items per wave with all loads of
 //              both items in flight at once.
+//   dealt      the step-like item (C = 1, M = 1) over a FIXED grid of G 1024-thread workgroups: wave wv of workgroup b takes
+//              the items (r * 16 + wv) * G + b, r = 0, 1, ... -- every workgroup holds the same number of busy waves (+- 1)
+//              whatever the item count, where the contiguous mapping fills items / 16 workgroups with sixteen each
 // usage: floor_bench [table_GiB=16]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -81,6 +84,24 @@ __global__ __launch_bounds__(1024, 8 / IPW) void rows_kernel(const RowArgs a) {
                 }
             }
         }
+    }
+}
+
+__global__ __launch_bounds__(1024, 8) void rows_dealt_kernel(const RowArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), G = gridDim.x;
+    for (int item = wv * G + (int)blockIdx.x; item < a.items; item += 16 * G) {
+        float *row = a.table + ((uint64_t)mix(item * 2654435761u + a.seed) % a.rows) * 512;
+        const float *g = a.grads + (uint64_t)item * 512;
+        f4 r0 = *(const f4 *)(row + 4 * lane), r1 = *(const f4 *)(row + 256 + 4 * lane);
+        const f4 g0 = *(const f4 *)(g + 4 * lane), g1 = *(const f4 *)(g + 256 + 4 * lane);
+        r0 -= 0.001f * g0;
+        r1 -= 0.001f * g1;
+        __builtin_nontemporal_store(r0, (f4 *)(row + 4 * lane));
+        __builtin_nontemporal_store(r1, (f4 *)(row + 256 + 4 * lane));
+        float *o = a.out + (uint64_t)item * 512;
+        __builtin_nontemporal_store(r0, (f4 *)(o + 4 * lane));
+        __builtin_nontemporal_store(r1, (f4 *)(o + 256 + 4 * lane));
     }
 }
 
@@ -202,5 +223,20 @@ int main(int argc, char **argv) {
     runf("apply-only, plain row stores", 6940, 1, 0, 256, 2);
     runf("apply-only, nt row loads", 6940, 1, 0, 256, 4);
     runf("apply-only, nt row loads + plain row stores", 6940, 1, 0, 256, 6);
+    // ---- dealt: a fixed grid, the items dealt over its workgroups; the contiguous rows of the same run beside them
+    printf("# step-like items dealt over a fixed grid of 1024-thread workgroups / contiguous (grid = items / waves per workgroup)\n");
+    for (int items : {5200, 7000}) {
+        run("contiguous", items, 1, 1, 1, 1024);
+        run("contiguous", items, 1, 1, 1, 256);
+        for (int G : {512, 480, 448}) {
+            const float us = time_launches(s, 1000, [&](int i) {
+                RowArgs b{table, rows, grads[i % NB], outs[i % NB], items, 1, 1, (uint32_t)(i * 7919u)};
+                hipLaunchKernelGGL(rows_dealt_kernel, dim3(G), dim3(1024), 0, s, b);
+            });
+            const double bytes = (double)items * 2048.0 * 4;
+            printf("dealt, grid %3d                    items %5d ipw 1 C 1 M 1 wg 1024: %6.2f us/launch  %.2f MB  %.2f TB/s\n", G, items, us,
+                   bytes / 1e6, bytes / us / 1e6);
+        }
+    }
     return 0;
 }
