@@ -35,10 +35,13 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
   --model emb_sum_wdl  the pooled Wide & Deep (examples/ctr/models/emb_sum_wdl_criteo.py): a sample's 26 rows are summed into one
                      before the tower (embedding_lookup_op + reduce_sum_op(axes=1)).  --embedding hbm: the fused sum-pooled
                      lookup (ha_gather_sum_*) and the bag apply (ha_sgd_apply_bags) -- neither [B, 26, d] nor the expanded
-                     gradient is built; ps / cache: per-occurrence rows as before, summed in the same order, the pooled
-                     gradient expanded before the push -- except --embedding cache --cache-planned --bsp 0, where the
-                     cache's planned pairs are pooled as well (ha_cache_lookup_sum_planned /
-                     ha_cache_update_planned_bags).  The step engines refuse the model.
+                     gradient is built; --embedding ps: pooled as well -- the sharded store sums a sample's rows out of the
+                     unique rows it received (pull_sum, ha_gather_sum_u32keys) and reduces the [B, d] gradient by unique key
+                     as it is (push_bags, ha_dedup_reduce_bags); what crosses the fabric is unchanged (--no-ps-fuse-bags:
+                     per-occurrence rows, the gradient expanded before the push; the same bits); cache: per-occurrence
+                     rows as before, summed in the same order, the pooled gradient expanded before the push -- except
+                     --embedding cache --cache-planned --bsp 0, where the cache's planned pairs are pooled as well
+                     (ha_cache_lookup_sum_planned / ha_cache_update_planned_bags).  The step engines refuse the model.
   --optimizer        the embedding table's optimizer on --embedding hbm: sgd (default), momentum, nesterov, adagrad, adam or adamw
                      with the reference's default hyper-parameters (python/hetu/optimizer.py:232-483); the states live beside
                      the table.  A pooled model's gradient goes to the optimizer pooled as well (ha_sparse_opt_fused_bags_*,
@@ -246,7 +249,7 @@ def make_batches(nbatch, batch, rows, seed=0, rank=0, world=1):
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
-          opt_fuse_bags=True):
+          opt_fuse_bags=True, ps_fuse_bags=True):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -254,7 +257,8 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     one cache call per training step, which needs cache_limit >= 2 * batch * 26 (the default limit takes that into account).
     A pooled model (emb_sum_wdl) on the planned pairs (bsp 0) pulls and pushes POOLED rows: the communicate op is told the bag
     size, the cache sums a sample's 26 rows as it reads them and takes the [batch, width] gradient as it is
-    (cache_fuse_bags=False: the unfused path, the same bits).
+    (cache_fuse_bags=False: the unfused path, the same bits).  On --embedding ps a pooled model does the same through the
+    sharded store's pull_sum / push_bags on every schedule (ps_fuse_bags=False, --no-ps-fuse-bags: the unfused path, the same bits).
     The ring wraps round, so the chain is still open when training ends, with one step's bookkeeping planned ahead and never
     run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
     replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests).
@@ -303,10 +307,11 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                  cstable_policy=cache if embedding == "cache" else None, cache_bound=bound,
                                  cache_limit=cache_limit if cache_limit is not None else
                                  max(rows // 10, batch * NFIELD * (2 if cache_planned and bsp < 0 else 1)),
-                                 cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned, cache_fuse_bags=cache_fuse_bags)
+                                 cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned, cache_fuse_bags=cache_fuse_bags,
+                                 ps_fuse_bags=ps_fuse_bags)
         comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: ids_of(state["k"] + 1),
                                                      peek_ids=lambda j: ids_of(state["k"] + 1 + j),
-                                                     bag=NFIELD if pooled and embedding == "cache" else None)
+                                                     bag=NFIELD if pooled and embedding in ("cache", "ps") else None)
         barrier = dist.barrier if world > 1 else (lambda: None)
         comm.forward_hook(config, first_ids=ids_of(0), barrier=barrier)
     if pooled:
@@ -469,6 +474,9 @@ def main():
                          "reads them and takes the [batch, width] gradient as it is, no [batch * 26, width] tensor; "
                          "--laia: the update pushes the batch's push plan).  With --laia at world size > 1 it is "
                          "accepted and has no effect (the cache there talks to a remote store, call by call)")
+    ap.add_argument("--no-ps-fuse-bags", action="store_true",
+                    help="--embedding ps with --model emb_sum_wdl: pull per-occurrence rows and push the expanded gradient "
+                         "instead of the store's pooled pull_sum / push_bags (the same bits)")
     ap.add_argument("--nepoch", type=int, default=-1, help="epochs of `--steps` steps each (default: one)")
     ap.add_argument("--embedding", choices=["hbm", "step", "step3", "queue", "ps", "cache"], default=None,
                     help="this build's engine names; default: from --comm / --cache")
@@ -514,7 +522,8 @@ def main():
         losses = train(args.embedding, args.rows, args.width, args.batch, args.steps, args.lr, args.cache,
                        args.bound, cache_limit=cache_limit, device="cuda:%d" % local_rank,
                        log_every=max(1, args.steps // 10), model=args.model, bsp=args.bsp if comm is not None else 0,
-                       cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer)[0]
+                       cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer,
+                       ps_fuse_bags=not args.no_ps_fuse_bags)[0]
     if local_rank == 0:
         print("first 10 steps: loss %.5f   last 10 steps: loss %.5f" % (np.mean(losses[:10]), np.mean(losses[-10:])))
 

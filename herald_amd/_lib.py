@@ -213,6 +213,8 @@ def _declare(L):
         "ha_sgd_sparse_update_f32ids": [vp, i64, i64, vp, i64, vp, f32, vp],
         "ha_gather_sum_f32ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp],
         "ha_gather_sum_u64ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp],
+        "ha_gather_sum_u32keys": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp],
+        "ha_dedup_reduce_bags": [vp, i64, vp, i64, i64, vp, f32, vp, vp],
         "ha_bag_of": [vp, i64, i64, vp, vp],
         "ha_sgd_apply_bags": [vp, i64, i64, vp, i64, vp, i64, vp, f32, vp],
         "ha_sgd_sparse_update_bags_f32ids": [vp, i64, i64, vp, i64, vp, i64, vp, i64, f32, vp],

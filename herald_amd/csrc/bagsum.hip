@@ -235,6 +235,14 @@ extern "C" int ha_gather_sum_u64ids(const float *table, int64_t rows, int64_t wi
                                         ha::as_stream(stream));
 }
 
+// The same over a buffer of rows named by uint32 keys held in device memory (the sharded store's pull: rows_buf = the unique rows
+// a batch received, keys = its plan's inverse[n]) -- the expand to [n, width] and the sum over it in one pass.
+extern "C" int ha_gather_sum_u32keys(const float *rows_buf, int64_t rows, int64_t width, const uint32_t *keys, int64_t n,
+                                     int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream) {
+    return ha::bag_sum_launch<uint32_t>("ha_gather_sum_u32keys", rows_buf, rows, width, keys, n, bag, offsets, nbags, out,
+                                        ha::as_stream(stream));
+}
+
 extern "C" int ha_bag_of(const int64_t *offsets, int64_t nbags, int64_t n, int32_t *bag_of, ha_stream_t stream) {
     HA_REQUIRE(nbags >= 0 && n >= 0 && nbags < (1ll << 31) && n < (1ll << 31), "ha_bag_of: bad sizes nbags=%ld n=%ld",
                (long)nbags, (long)n);

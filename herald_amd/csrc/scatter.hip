@@ -87,7 +87,7 @@ __global__ __launch_bounds__(1024, 8) void apply_mapped2_kernel(
 // batch sit inside long runs, so here a fixed grid of workgroups loops over the unique keys instead
 // (uniq / seg / counts of the plan): short and medium runs are applied by the wave that owns the key,
 // keys with >= kLongRun occurrences are collected in a list ...
-// BAGS (kModeOpt on pooled gradients, ha_sparse_opt_fused_bags_*): the source row of an occurrence goes through
+// BAGS (pooled gradients: kModeOpt, ha_sparse_opt_fused_bags_*, and kModeReduce, ha_dedup_reduce_bags): the source row of an occurrence goes through
 // ApplyMaps::valmap / valdiv in every run class (src_row, scatter_dev.h); false compiles to what it always was.
 template <int MODE, int VEC, bool BAGS = false>
 __global__ __launch_bounds__(1024, 8) void apply_unique_kernel(
@@ -507,7 +507,7 @@ static int apply_launch(float *dst, int64_t dst_rows, int64_t width,
 
 // apply of a FINISHED plan by unique key (larger batches); plan scratch keys_alt holds the long list
 namespace ha {
-// BAGS: the kernels' BAGS instantiations (source rows through maps.valmap / maps.valdiv; kModeOpt only)
+// BAGS: the kernels' BAGS instantiations (source rows through maps.valmap / maps.valdiv; kModeOpt and kModeReduce)
 template <int MODE, bool BAGS>
 static int apply_by_unique_impl(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, int64_t n,
                                 const float *grads, float lr, hipStream_t stream, ApplyMaps maps) {
@@ -838,6 +838,102 @@ extern "C" int ha_dedup_reduce_scaled(const void *plan_ws, int64_t n,
                                       ha_stream_t stream) {
     return ha::apply_launch<ha::kModeReduce>(reduced, n, width, plan_ws, n,
                                              grads, scale, ha::as_stream(stream));
+}
+
+// ---- dedup-reduce of POOLED gradients (the worker side of a PS sparse push of a sum-pooled lookup) ---------------------
+// ha_dedup_reduce_scaled on bag_grads expanded to [n, width], without the expanded tensor: the gradient row of occurrence i is
+// the row of its bag (i / bag in registers for fixed bags, bag_of[i] for ragged ones).  The bodies are those of the expanded
+// call -- apply_kernel<kModeReduce> by sorted position up to kSmallMax ids, the by-unique kernels of a FINISHED plan beyond --
+// in their BAGS instantiations, so the same runs take the same chain or tree over the same values: the same bits.
+namespace ha {
+template <int VEC, bool FIXED>
+__global__ __launch_bounds__(1024, 8) void reduce_bags_kernel(
+    float *__restrict__ dst, uint64_t dst_rows, int width,
+    const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
+    const int32_t *__restrict__ upos, int n, const float *__restrict__ bag_grads,
+    float scale, int tree_from, int bag, const int32_t *__restrict__ bag_of) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
+    ApplyMaps maps{};
+    maps.tree_from = tree_from;
+    maps.valmap = FIXED ? nullptr : bag_of;
+    maps.valdiv = FIXED ? bag : 0;
+    apply_body<kModeReduce, VEC, false, kHandNone, true>(dst, dst_rows, width, sorted, perm, upos, n, bag_grads, scale, blockIdx.x, s_apply, nullptr, maps);
+}
+
+// out[i,:] = bag_grads[bag of i,:] (tolerance mode 2 only, see ha_dedup_reduce_bags): one thread per element
+__global__ __launch_bounds__(256) void expand_bags_kernel(const float *__restrict__ bag_grads, int width, int64_t n, int bag,
+                                                          const int32_t *__restrict__ bag_of, float *__restrict__ out) {
+    const int64_t total = n * width;
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; e < total; e += static_cast<int64_t>(gridDim.x) * 256) {
+        const int64_t i = e / width;
+        const int c = static_cast<int>(e - i * width);
+        const int64_t b = bag_of ? static_cast<int64_t>(bag_of[i]) : i / bag;
+        out[e] = bag_grads[b * width + c];
+    }
+}
+}  // namespace ha
+
+extern "C" int ha_dedup_reduce_bags(const void *plan_ws, int64_t n, const float *bag_grads, int64_t width, int64_t bag,
+                                    const int32_t *bag_of, float scale, float *reduced, ha_stream_t stream) {
+    using namespace ha;
+    HA_REQUIRE(n >= 0 && width >= 1 && width < (1 << 30) && n < (1ll << 31), "ha_dedup_reduce_bags: bad sizes n=%ld width=%ld",
+               (long)n, (long)width);
+    HA_REQUIRE((bag >= 1) != (bag_of != nullptr), "ha_dedup_reduce_bags: give exactly one of bag >= 1 and bag_of (bag=%ld)",
+               (long)bag);
+    HA_REQUIRE(bag_of != nullptr || (bag < (1ll << 31) && n % bag == 0),
+               "ha_dedup_reduce_bags: n=%ld is not a multiple of bag=%ld", (long)n, (long)bag);
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(plan_ws && bag_grads && reduced, "ha_dedup_reduce_bags: null pointer");
+    hipStream_t s = as_stream(stream);
+    const bool fixed = bag_of == nullptr;
+    if (n > kSmallMax) {      // a FINISHED plan: waves map to unique keys
+        // tolerance mode 2 cuts the long runs of a plain launch into chunks (apply_by_unique_impl's own conditions: the 16-byte
+        // path, at most four slices; the expanded gradient would be aligned scratch); there are no chunked bags: expand, then
+        // that launch.  Where the expanded call would not chunk, the bag kernels below take the same trees as it does.
+        const bool would_chunk = g_tree_chunks && tolerance_tree_from() > 0 && n <= kFinishChunkedMax && width % 4 == 0 &&
+                                 reinterpret_cast<uintptr_t>(reduced) % 16 == 0 && (width + kWave - 1) / kWave <= 4;
+        if (would_chunk) {
+            void *ws = nullptr;
+            if (scratch_get(s, static_cast<size_t>(n) * width * sizeof(float), &ws))
+                return -1;
+            hipLaunchKernelGGL(expand_bags_kernel, dim3(2048), dim3(256), 0, s, bag_grads, (int)width, n, (int)bag, bag_of,
+                               static_cast<float *>(ws));
+            HA_LAUNCH_CHECK();
+            return apply_launch<kModeReduce>(reduced, n, width, plan_ws, n, static_cast<const float *>(ws), scale, s);
+        }
+        ApplyMaps maps{};
+        maps.valmap = bag_of;
+        maps.valdiv = fixed ? static_cast<int>(bag) : 0;
+        return apply_by_unique_impl<kModeReduce, true>(reduced, n, width, const_cast<void *>(plan_ws), n, bag_grads, scale, s,
+                                                       maps);
+    }
+    ha_plan_view v;
+    if (ha_plan_view_of(const_cast<void *>(plan_ws), n, &v) != 0)
+        return -1;
+    const unsigned blocks = static_cast<unsigned>((n + kPosPerBlock - 1) / kPosPerBlock);
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(reduced) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(bag_grads) % 16 == 0);
+    static DeviceOnce lds_allowed;
+    if (lds_allowed.run([]() -> int {
+            HA_ALLOW_LDS((reduce_bags_kernel<4, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((reduce_bags_kernel<4, false>), kApplyLdsBytes);
+            HA_ALLOW_LDS((reduce_bags_kernel<1, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((reduce_bags_kernel<1, false>), kApplyLdsBytes);
+            return 0;
+        }))
+        return -1;
+#define HA_RBAGS_CASE(V, F)                                                                                              \
+    hipLaunchKernelGGL((reduce_bags_kernel<V, F>), dim3(blocks), dim3(1024), kApplyLdsBytes, s, reduced, (uint64_t)n,    \
+                       (int)width, v.sorted, v.perm, v.upos, (int)n, bag_grads, scale, tolerance_tree_from(), (int)bag,  \
+                       bag_of)
+    if (vec_ok && fixed) HA_RBAGS_CASE(4, true);
+    else if (vec_ok) HA_RBAGS_CASE(4, false);
+    else if (fixed) HA_RBAGS_CASE(1, true);
+    else HA_RBAGS_CASE(1, false);
+#undef HA_RBAGS_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
 }
 
 // Development aid (tools/timeline.py): SGD apply with per-wave {start, end, role, cycles} stamps

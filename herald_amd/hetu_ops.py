@@ -12,8 +12,9 @@ Mirrors (paths relative to /root/reference):
                                                   straight from the pooled gradient of EmbeddingLookUpSum_Gradient)
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
-cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and two switches of this build: cache_plan_ahead (the cache's
-planned flow) and cache_fuse_bags (with it, at bsp 0: a sum-pooled lookup is pulled and pushed pooled, see Config).  The data loader contract is the reference's
+cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and three switches of this build: cache_plan_ahead (the cache's
+planned flow), cache_fuse_bags (with it, at bsp 0: a sum-pooled lookup is pulled and pushed pooled, see Config) and
+ps_fuse_bags (the same on the plain PS flavour, every schedule).  The data loader contract is the reference's
 `get_arr` / `get_next_arr` (python/hetu/dataloader.py:63-98): `next_ids()` returns the ids of the batch
 after the current one.  Everything computed goes through libherald_amd.so.
 """
@@ -28,7 +29,8 @@ from .sharded import ShardedEmbedding
 
 class Config:
     def __init__(self, comm_mode=None, bsp=0, prefetch=True, cstable_policy=None, cache_bound=100, cache_limit=0,
-                 use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False, cache_fuse_bags=True):
+                 use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False, cache_fuse_bags=True,
+                 ps_fuse_bags=True):
         self.comm_mode, self.bsp, self.prefetch = comm_mode, bsp, prefetch
         # not a HetuConfig field: the cache's PLANNED flow (csrc/cache_block.hip) for the bsp-prefetch schedule -- the bookkeeping
         # of batch k + 1 runs on a side stream beside the model's step on batch k.  Needs ids one batch further ahead than
@@ -41,6 +43,13 @@ class Config:
         # tensor on either side, the same bits.  False: the unfused path (per-occurrence rows, a summing pass, the expanded
         # gradient).  Every other schedule -- the asp chain, ssp, no prefetch, world > 1, the call-by-call cache -- is unfused.
         self.cache_fuse_bags = cache_fuse_bags
+        # the same switch for the plain PS flavour (no cstable_policy; ssp, asp and no prefetch alike): a communicate op that
+        # was told its bag size pulls pooled rows (ShardedEmbedding.pull_sum) and pushes the pooled gradient (push_bags), and
+        # without prefetch EmbeddingLookUpSum pulls pooled rows itself (ragged bags too) -- that lookup reads this switch alone:
+        # it is pooled whether or not the communicate op was given bag=, which decides the op's own pulls and pushes only.
+        # What crosses the fabric does not change -- rows per unique key --, the same bits.  False: per-occurrence rows, a
+        # summing pass, the expanded gradient.
+        self.ps_fuse_bags = ps_fuse_bags
         self.cstable_policy, self.cache_bound, self.cache_limit = cstable_policy, cache_bound, cache_limit
         self.use_sparse_pull = use_sparse_pull
         self.cache_perf_enable = cache_perf_enable        # executor.py: cache_perf_enable (run_hetu.py:508-515 dumps the dicts)
@@ -131,9 +140,13 @@ class EmbeddingLookUpSum(EmbeddingLookUp):
     (examples/ctr/models/emb_sum_wdl_criteo.py:14-16): compute(ids[B, F], output_val[B, width]) -- or ids[n] with
     offsets[B + 1] for ragged bags.  With a device table it is the fused kernel (ops.embedding_lookup_sum).  On the PS, cache
     and prefetched paths the per-occurrence rows arrive as EmbeddingLookUp delivers them and the same kernel sums them, in the
-    same position order, out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Those paths are
-    not fused: they still move [n, width] rows -- except the cache's planned pairs (Config.cache_fuse_bags), where the
-    communicate op's buffer already holds the pooled rows (the cache summed them as it read them) and is copied as it is."""
+    same position order, out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Two of those
+    paths are fused as well: the cache's planned pairs (Config.cache_fuse_bags) and the plain PS flavour
+    (Config.ps_fuse_bags) -- with prefetch the communicate op's buffer already holds the pooled rows (the cache, or the
+    sharded store's pull_sum, summed them as it read them) and is copied as it is; without prefetch the rows come from
+    store.pull_sum directly, ragged bags included, whether or not the communicate op was told a bag size (`stream` is not
+    used there: the store works on the current stream, as its pull does).  The call-by-call cache and ps_fuse_bags=False still
+    move [n, width] rows."""
 
     def forward_hook(self, config):
         super().forward_hook(config)
@@ -151,6 +164,8 @@ class EmbeddingLookUpSum(EmbeddingLookUp):
                 raise ValueError("EmbeddingLookUpSum: the communicate op pulls pooled rows for fixed bags of %d ids"
                                  % self.config.ps_pooled[self.embedding])
             return self._compute_prefetched(ids, output_val, stream)      # a pooled buffer, as it is
+        if self._rows_compute == self._compute_sparsepull_from_ps and getattr(self.config, "ps_fuse_bags", True):
+            return self.embedding.store.pull_sum(ids, offsets=offsets, out=output_val)
         n, width = ids.numel(), self.embedding.shape[1]
         if self._pos is None or self._pos.numel() < n or self._pos.device != output_val.device:
             self._pos = torch.arange(max(n, 1), dtype=torch.int64, device=output_val.device)
@@ -313,15 +328,19 @@ class ParameterServerCommunicateOp:
         """peek_ids(j) (optional, Config.cache_plan_ahead): the ids of the batch j batches after the one next_ids() returns
         (peek_ids(0) = that batch itself), without advancing the loader; None when there is none.
         bag (optional): the embedding is read through a sum-pooled lookup (EmbeddingLookUpSum) with fixed bags of `bag` ids --
-        ids arrive as [B, bag].  With the cache's planned pairs and Config.cache_fuse_bags the op then keeps sparse_pull_val as
-        [B, width] and moves pooled rows and pooled gradients only; on every other schedule it changes nothing."""
+        ids arrive as [B, bag].  With the cache's planned pairs and Config.cache_fuse_bags, or on the plain PS flavour with
+        Config.ps_fuse_bags, the op then keeps sparse_pull_val as [B, width] and moves pooled rows and pooled gradients only;
+        on every other path (the call-by-call cache, the asp chain, the cache over a sharded store) it changes nothing.
+        Without bag= the op's pulls and pushes are per occurrence as they always were; the lookup without prefetch
+        (EmbeddingLookUpSum -> store.pull_sum) does not pass through this op and follows Config.ps_fuse_bags alone."""
         self.parameter = parameter
         self.learning_rate = -learning_rate                           # :24
         self.next_ids = next_ids
         self.peek_ids = peek_ids
         self._peek_offset = 1
         self.bag = int(bag) if bag is not None else None
-        self._bag = None              # the bag size while the pooled planned pairs are in use (forward_hook decides)
+        self._bag = None              # the bag size while pooled rows are pulled and pushed (forward_hook decides)
+        self._ps_bags = False         # ... by the plain PS flavour (store.pull_sum / push_bags)
         self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
         self._chain = False           # the planned flow of the asp schedule: _planned = ids of a push-pull chain's batches
 
@@ -375,6 +394,8 @@ class ParameterServerCommunicateOp:
                 self.compute = self._compute_no_prefetch
         else:
             self._push, self._pull, self._push_pull = self._push_sparse, self._pull_sparse, self._push_pull_sparse
+            if self.bag is not None and getattr(config, "ps_fuse_bags", True):
+                self._bag, self._ps_bags = self.bag, True
             # :235-242: bsp >= 0 -> ssp (push, ssp_sync(version), pull), else asp (push_pull) when prefetching
             if config.prefetch and config.bsp >= 0:
                 self.compute = self._compute_ssp_prefetch
@@ -406,13 +427,16 @@ class ParameterServerCommunicateOp:
     # -- compute variants (:37-56)
     def _per_occurrence(self, grad):
         """Pooled slices (the gradient of EmbeddingLookUpSum: one row per bag) are expanded to per-occurrence values before
-        they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The PS, cache and
-        step-engine paths are NOT fused for pooled access: they move the expanded [n, width] values as they always did.  The
-        cache's planned pairs are (Config.cache_fuse_bags): slices pooled by the op's own bag size stay [B, width]; -lr is
-        applied to those rows only, which is the same product for every occurrence of a bag."""
+        they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The call-by-call
+        cache and the step engines are NOT fused for pooled access: they move the expanded [n, width] values as they always
+        did.  The cache's planned pairs (Config.cache_fuse_bags) and the plain PS flavour (Config.ps_fuse_bags) are: slices
+        pooled by the op's own bag size stay [B, width] -- on the PS flavour ragged slices that carry their offsets too --;
+        -lr is applied to those rows only, which is the same product for every occurrence of a bag."""
         if not getattr(grad, "pooled", False):
             return grad
         if self._bag is not None and grad.bag == self._bag:
+            return grad
+        if self._ps_bags and grad.bag is None and grad.offsets is not None:
             return grad
         return ops.IndexedSlices(indices=grad.indices, values=grad.expanded_values(), dense_shape=grad.dense_shape,
                                  push_indices=grad.push_indices)
@@ -563,12 +587,26 @@ class ParameterServerCommunicateOp:
 
     # -- plain PS flavour (SparsePush / SparsePull / SSPushPull, :74-111); values are already scaled
     def _push_sparse(self, grad):
+        if self._ps_bags and getattr(grad, "pooled", False):      # (what _per_occurrence left pooled: values is [B, width])
+            width = self.parameter.shape[1]
+            if grad.bag is not None:
+                self.parameter.store.push_bags(grad.indices.reshape(-1, int(grad.bag)), grad.values.reshape(-1, width))
+            else:
+                self.parameter.store.push_bags(grad.indices.reshape(-1), grad.values.reshape(-1, width),
+                                               offsets=grad.offsets)
+            return None
         self.parameter.store.push(grad.indices, grad.values)
         return None
 
     def _pull_sparse(self, ids):
         if isinstance(ids, tuple):
             ids = ids[0]
+        if self._ps_bags:
+            if ids.dim() != 2 or ids.shape[1] != self._bag:
+                raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
+                                 % (self._bag, self._bag, tuple(ids.shape)))
+            self.parameter.store.pull_sum(ids, out=self.sparse_pull_val)
+            return None
         self.sparse_pull_val.copy_(self.parameter.store.pull(ids))
         return None
 

@@ -353,6 +353,73 @@ def embedding_lookup_sum(table, ids, offsets=None, out=None, stream=None):
     return out
 
 
+def gather_sum_u32keys(rows_buf, keys_i32, bag=None, offsets=None, out=None, stream=None):
+    """embedding_lookup_sum over a buffer of rows named by uint32 keys held in an int32 tensor (a plan's inverse(): the pull
+    of the sharded store sums a batch's bags straight out of the unique rows it received).  Fixed bags: keys [B, F], or
+    keys [n] with bag=F; ragged bags: keys [n] with offsets int64 [B + 1].  Returns out [B, width]."""
+    L = _lib.load()
+    _require(rows_buf, torch.float32, "rows_buf")
+    if rows_buf.dim() != 2:
+        raise ValueError("rows_buf must be 2-D")
+    _require(keys_i32, torch.int32, "keys")
+    n = keys_i32.numel()
+    if offsets is not None:
+        if bag is not None:
+            raise ValueError("give at most one of bag and offsets")
+        _require(offsets, torch.int64, "offsets")
+        if offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("ragged bags need offsets of shape [B + 1]")
+        bag, nbags = 0, offsets.numel() - 1
+    else:
+        if bag is None:
+            if keys_i32.dim() != 2:
+                raise ValueError("fixed bags need keys of shape [B, F] or bag=F; give offsets for ragged bags")
+            bag = keys_i32.shape[1]
+        bag = int(bag)
+        if bag < 1 or n % bag:
+            raise ValueError("%d keys are not bags of %d" % (n, bag))
+        nbags = n // bag
+    width = rows_buf.shape[1]
+    if out is None:
+        out = torch.empty((nbags, width), dtype=torch.float32, device=rows_buf.device)
+    _require(out, torch.float32, "out")
+    if out.numel() != nbags * width:
+        raise ValueError("out has the wrong size")
+    check(L.ha_gather_sum_u32keys(_ptr(rows_buf), rows_buf.shape[0], width, _ptr(keys_i32), n, bag,
+                                  _ptr(offsets) if offsets is not None else None, nbags, _ptr(out), _stream_ptr(stream)),
+          "ha_gather_sum_u32keys")
+    return out
+
+
+def dedup_reduce_bags(plan, bag_grads, bag=None, bag_of=None, scale=None, out=None, stream=None):
+    """dedup_reduce on the POOLED gradient bag_grads [B, width] of a sum-pooled lookup: reduced[u,:] = sum of (scale *) the
+    bag rows of unique key u's occurrences in occurrence order -- bit for bit dedup_reduce on bag_grads expanded to
+    [n, width].  Give `bag` (fixed bags of that many ids) or `bag_of` (int32 [n], from ops.bag_of).  Beyond 36,864 ids the
+    plan must be finished (build(), or sort() + finish()), as for dedup_reduce."""
+    _require(bag_grads, torch.float32, "bag_grads")
+    if bag_grads.dim() != 2:
+        raise ValueError("bag_grads must be [B, width]")
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    n, width = plan.n, bag_grads.shape[1]
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != n:
+            raise ValueError("bag_of must have one entry per planned id")
+    elif bag < 1 or n % bag or bag_grads.shape[0] != n // bag:
+        raise ValueError("bag_grads must be [n / bag, width]")
+    if out is None:
+        out = torch.empty((max(n, 1), width), dtype=torch.float32, device=bag_grads.device)
+    _require(out, torch.float32, "out")
+    if out.numel() < n * width:
+        raise ValueError("out must hold n rows")
+    check(_lib.load().ha_dedup_reduce_bags(_ptr(plan.ws), n, _ptr(bag_grads), width, int(bag) if bag is not None else 0,
+                                           _ptr(bag_of) if bag_of is not None else None,
+                                           ctypes.c_float(1.0 if scale is None else scale), _ptr(out), _stream_ptr(stream)),
+          "ha_dedup_reduce_bags")
+    return out
+
+
 def bag_of(offsets, n, out=None, stream=None):
     """int32 [n]: the bag of every occurrence of ragged bags (what sgd_apply_bags takes)."""
     _require(offsets, torch.int64, "offsets")

@@ -19,6 +19,9 @@ over RCCL (torch.distributed "nccl" backend == RCCL over xGMI):
     route: [count | shard-local keys] frames, ONE equal-split exchange   (once per batch, shared by pull and push)
     pull : [owner gathers]  ->  rows back  ->  [expand to the positions]
     push : [worker dedup-reduces]  ->  reduced rows  ->  [owner applies, rank order]
+A sum-pooled model (embedding_lookup_op + reduce_sum_op(axes=1), examples/ctr/models/emb_sum_*.py) changes the two steps at
+the worker's end only -- pull_sum sums each bag as it expands, push_bags reduces the pooled gradient [B, width] as it is --
+and nothing that travels: rows per unique key, both ways.
 The routing of a batch depends on its ids only, and the ids are known one step ahead (the reference
 prefetches them too: ParameterServerCommunicate.py:96-139), so `prefetch(ids)` enqueues it ahead of the
 row exchanges of the current batch; the only host read-back of a step (n_unique and the 2W counts, which
@@ -217,6 +220,22 @@ class HipEngine:
                                                    ctypes.c_float(scale), out.data_ptr(), self._stream()),
                    "ha_dedup_reduce_scaled")
         return out
+
+    # -- sum-pooled access: the two end kernels of pull_sum / push_bags (what crosses the fabric is unchanged) ----------
+    def expand_sum(self, rows, plan, bag=None, offsets=None, out=None):
+        """out[b,:] = ((0 + rows[inverse[i0],:]) + rows[inverse[i1],:]) + ... over the positions of bag b in order: expand
+        followed by the sum over each bag, without the [n, width] rows in between.  Fixed bags of `bag` ids, or ragged
+        ones by int64 offsets[B + 1] on the device."""
+        return self.ops.gather_sum_u32keys(rows, plan.inverse(), bag=bag, offsets=offsets, out=out, stream=self._stream())
+
+    def reduce_scaled_bags(self, plan, bag_values, scale, bag=None, bag_of=None, offsets=None):
+        """reduce_scaled on the pooled values [B, width]: position i contributes the row of its bag -- i // bag, or
+        bag_of[i] (int32 [n]; built here from int64 offsets[B + 1] when those are given instead)."""
+        if offsets is not None:
+            bag_of = self.ops.bag_of(offsets, plan.n, stream=self._stream())
+        out = self._buf("reduced", max(plan.n, 1), bag_values.shape[1])
+        return self.ops.dedup_reduce_bags(plan, bag_values, bag=bag, bag_of=bag_of, scale=scale, out=out,
+                                          stream=self._stream())
 
     def acc_apply(self, table, keys_i32, values):
         """table[key,:] = (table[key,:] + v_a) + v_b ... in the order the (key, value) pairs are listed."""
@@ -845,6 +864,82 @@ class ShardedEmbedding:
     def push_pull(self, push_ids, values, lr, pull_ids):
         self.push(push_ids, values, lr)
         return self.pull(pull_ids)
+
+    # -- sum-pooled access (embedding_lookup_op + reduce_sum_op(axes=1) of the reference's emb_sum_* models on the PS) -----
+    # The same keys and rows cross the fabric as in pull / push -- rows per unique key, both ways -- so routing, owner gather,
+    # exchanges, owner apply and `stats` are theirs; only this rank's two end kernels differ: the received unique rows are
+    # summed per bag as they are expanded (no [n, width] rows), and the pooled gradient [B, width] is reduced by unique key
+    # as it is (no expanded [n, width] values).  Bit for bit pull + sum / expand + push.
+    def _bag_layout(self, what, ids, offsets, route):
+        """(bag, nbags) of a call: fixed bags from ids [B, F] (or the route's recorded shape), ragged ones from ids [n] +
+        int64 offsets[B + 1] on the store's device.  Raises ValueError -- before the caller enters any collective."""
+        if ids is None and route is None:
+            raise ValueError("%s: give ids or a route" % what)
+        shape = tuple(ids.shape) if ids is not None else route.shape
+        if offsets is None:
+            if len(shape) != 2 or shape[1] < 1:
+                raise ValueError("%s: fixed bags need ids of shape [B, F], got %s; give offsets for ragged bags"
+                                 % (what, shape))
+            return int(shape[1]), int(shape[0])
+        if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.device != self.table.device:
+            raise ValueError("%s: offsets must be an int64 tensor on %s" % (what, self.table.device))
+        if len(shape) != 1 or offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
+            raise ValueError("%s: ragged bags need ids of shape [n] and contiguous offsets of shape [B + 1]" % what)
+        return None, int(offsets.numel()) - 1
+
+    def _check_bag_values(self, what, bag_values, nbags):
+        if not isinstance(bag_values, torch.Tensor) or bag_values.dim() != 2 or \
+                tuple(bag_values.shape) != (nbags, self.width) or bag_values.dtype != torch.float32:
+            raise ValueError("%s: bag_values must be float32 [B, width] = [%d, %d], got %s"
+                             % (what, nbags, self.width, tuple(getattr(bag_values, "shape", ()))))
+
+    def pull_sum(self, ids=None, offsets=None, route=None, return_route=False, out=None):
+        """out[b,:] = ((0 + table_global[id_0,:]) + table_global[id_1,:]) + ... over bag b's ids in position order: pull
+        followed by the sum over each bag.  ids [B, F] (fixed bags; or the shape a prefetched route recorded), or ids [n]
+        with int64 offsets[B + 1] on the device (ragged bags).  Returns [B, width]."""
+        bag, nbags = self._bag_layout("pull_sum", ids, offsets, route)
+        if out is not None and (tuple(out.shape) != (nbags, self.width) or out.dtype != torch.float32 or
+                                not out.is_contiguous()):
+            raise ValueError("pull_sum: out must be contiguous float32 [%d, %d]" % (nbags, self.width))
+        eng = self.engine
+        if route is None:
+            route = self.prefetch(ids)
+        r = self.complete(route)
+        eng.wait_event(r.ready)
+        rows_send = eng.gather_keys(self.table, r.keys_recv, scratch="pull_send")
+        rows_recv = eng.rows_buffer("pull_recv", r.u, self.width)
+        self._a2a(rows_recv, rows_send, r.send_cnt, r.recv_cnt)
+        out = eng.expand_sum(rows_recv, r.plan, bag=bag, offsets=offsets, out=out)
+        self._account(r.send_cnt, r.recv_cnt, 4, 4 * self.width)
+        self._release(r)
+        return (out, r) if return_route else out
+
+    def push_bags(self, ids, bag_values, lr=None, offsets=None, route=None):
+        """push of the pooled values bag_values [B, width]: every id of bag b pushes -lr * bag_values[b,:] (scale 1 if lr
+        is None) -- push(ids, bag_values expanded to [n, width], lr) without the expanded values."""
+        bag, nbags = self._bag_layout("push_bags", ids, offsets, route)
+        self._check_bag_values("push_bags", bag_values, nbags)
+        eng = self.engine
+        if route is None:
+            route = self.prefetch(ids)
+        r = self.complete(route)
+        scale = 1.0 if lr is None else -float(lr)
+        eng.wait_event(r.ready)   # the plan and the keys were produced on the side stream
+        reduced = eng.reduce_scaled_bags(r.plan, bag_values.contiguous(), scale, bag=bag, offsets=offsets)
+        rows_send = reduced[:r.u]
+        rows_recv = eng.rows_buffer("push_recv", sum(r.recv_cnt), self.width)
+        self._a2a(rows_recv, rows_send, r.recv_cnt, r.send_cnt)
+        eng.acc_apply(self.table, r.keys_recv, rows_recv)
+        self._account(r.send_cnt, r.recv_cnt, 4 * self.width, 0)
+        self._release(r)
+
+    def push_pull_bags(self, push_ids, bag_values, lr, pull_ids, push_offsets=None, pull_offsets=None):
+        """push_bags of this batch, then pull_sum of the next one (SSPushPull on pooled access)."""
+        _, nbags = self._bag_layout("push_pull_bags (push)", push_ids, push_offsets, None)
+        self._check_bag_values("push_pull_bags", bag_values, nbags)
+        self._bag_layout("push_pull_bags (pull)", pull_ids, pull_offsets, None)
+        self.push_bags(push_ids, bag_values, lr, offsets=push_offsets)
+        return self.pull_sum(pull_ids, offsets=pull_offsets)
 
     # -- checkpoint format of the reference: raw fp32 `<name>_<part>.dat` per shard ------------------------
     CKPT_CHUNK_BYTES = 64 << 20

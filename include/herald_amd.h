@@ -1258,6 +1258,13 @@ int ha_gather_sum_f32ids(const float *table, int64_t rows, int64_t width, const 
                          const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
 int ha_gather_sum_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
                          const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
+/* The same with the rows named by uint32 keys (device uint32[n]) into a buffer of rows: the contract of
+ * ha_gather_sum_f32ids to the letter -- position-ordered chain, a key >= rows adds a zero row, clamped offsets, the same
+ * slice rule and ha_debug_bag_slice.  The pull of the row-sharded store (herald_amd/sharded.py, pull_sum): rows_buf is
+ * the [u, width] buffer of the unique rows a batch received and keys its plan's inverse[n], so the per-occurrence rows
+ * [n, width] are neither written nor read back. */
+int ha_gather_sum_u32keys(const float *rows_buf, int64_t rows, int64_t width, const uint32_t *keys, int64_t n, int64_t bag,
+                          const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
 /* bag_of[i] (int32[n]) = the bag of occurrence i of ragged bags; always in [0, nbags). */
 int ha_bag_of(const int64_t *offsets, int64_t nbags, int64_t n, int32_t *bag_of, ha_stream_t stream);
 /* Backward: bag_grads is the gradient of the pooled output, [nbags, width]; occurrence i takes the row of its bag:
@@ -1269,6 +1276,23 @@ int ha_bag_of(const int64_t *offsets, int64_t nbags, int64_t n, int32_t *bag_of,
  * bag_grads).  One wave per sorted position for every n. */
 int ha_sgd_apply_bags(float *table, int64_t rows, int64_t width, const void *plan_ws, int64_t n, const float *bag_grads,
                       int64_t bag, const int32_t *bag_of, float lr, ha_stream_t stream);
+/* ha_dedup_reduce_scaled on the pooled gradient: the worker side of a PS sparse push of a sum-pooled lookup,
+ *   reduced[u,:] = (0 + scale * bag_grads[bag_of(i0),:]) + scale * bag_grads[bag_of(i1),:] + ...
+ * over the occurrences i0 < i1 < ... of unique key u -- bit for bit ha_dedup_reduce_scaled on bag_grads expanded to
+ * [n, width], on every path that call takes (by sorted position up to 36,864 ids; by unique key of a FINISHED plan
+ * beyond, which is what plan_ws must then be) and in tolerance modes 0 and 1 (the same runs take the same chain or tree).
+ * Exactly one of bag >= 1 (fixed bags, bag_of NULL, n % bag == 0) and bag_of (int32[n] from ha_bag_of, bag == 0), as
+ * ha_sgd_apply_bags; every entry of bag_of must name a row of bag_grads.  reduced holds n rows, the first n_unique are
+ * written.  width % 4 == 0 with 16-byte aligned bag_grads / reduced takes the 16-byte path, anything else the scalar one.
+ * Tolerance mode 2 cuts long runs into chunks in plain launches only and there are no chunked bags: in that mode a batch
+ * of 36,865 .. 2^20 ids that the expanded call would chunk (width % 4 == 0, width <= 256, 16-byte aligned reduced) is
+ * expanded into the library's per-stream scratch (n * width floats) and goes through ha_dedup_reduce_scaled's own launch
+ * -- the same bits as that call in mode 2 on a 16-byte aligned expanded gradient, without the saving.  That scratch is
+ * the one the one-call entry points (ha_sgd_sparse_update_*, ...) use on the same stream, and it is freed and allocated
+ * anew when it has to grow: plan_ws, bag_of, bag_grads and reduced must be the caller's own allocations, never pointers
+ * into it.  Arguments are checked before any device access. */
+int ha_dedup_reduce_bags(const void *plan_ws, int64_t n, const float *bag_grads, int64_t width, int64_t bag,
+                         const int32_t *bag_of, float scale, float *reduced, ha_stream_t stream);
 /* One call: plan + (ha_bag_of +) ha_sgd_apply_bags, on an internal per-stream workspace. */
 int ha_sgd_sparse_update_bags_f32ids(float *table, int64_t rows, int64_t width, const float *ids, int64_t n,
                                      const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags, float lr,
