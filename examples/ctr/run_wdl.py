@@ -40,8 +40,9 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      as it is (push_bags, ha_dedup_reduce_bags); what crosses the fabric is unchanged (--no-ps-fuse-bags:
                      per-occurrence rows, the gradient expanded before the push; the same bits); cache: per-occurrence
                      rows as before, summed in the same order, the pooled gradient expanded before the push -- except
-                     --embedding cache --cache-planned --bsp 0, where the cache's planned pairs are pooled as well
-                     (ha_cache_lookup_sum_planned / ha_cache_update_planned_bags).  The step engines refuse the model.
+                     --embedding cache --cache-planned, where the cache's planned flow is pooled as well: the pairs at
+                     --bsp 0 (ha_cache_lookup_sum_planned / ha_cache_update_planned_bags) and, at the default --bsp -1 with
+                     --cache lru, the push-pull chain (ha_cache_push_pull_planned_bags).  The step engines refuse the model.
   --optimizer        the embedding table's optimizer on --embedding hbm: sgd (default), momentum, nesterov, adagrad, adam or adamw
                      with the reference's default hyper-parameters (python/hetu/optimizer.py:232-483); the states live beside
                      the table.  A pooled model's gradient goes to the optimizer pooled as well (ha_sparse_opt_fused_bags_*,
@@ -255,9 +256,9 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
     planned lookup + update pairs; at bsp < 0 (asp, the command line's default) with the LRU policy the planned push-pull chain:
     one cache call per training step, which needs cache_limit >= 2 * batch * 26 (the default limit takes that into account).
-    A pooled model (emb_sum_wdl) on the planned pairs (bsp 0) pulls and pushes POOLED rows: the communicate op is told the bag
-    size, the cache sums a sample's 26 rows as it reads them and takes the [batch, width] gradient as it is
-    (cache_fuse_bags=False: the unfused path, the same bits).  On --embedding ps a pooled model does the same through the
+    A pooled model (emb_sum_wdl) on the planned pairs (bsp 0) and on the planned push-pull chain (bsp < 0, LRU) pulls and pushes
+    POOLED rows: the communicate op is told the bag size, the cache sums a sample's 26 rows as it reads them and takes the
+    [batch, width] gradient as it is (cache_fuse_bags=False: the unfused path, the same bits).  On --embedding ps a pooled model does the same through the
     sharded store's pull_sum / push_bags on every schedule (ps_fuse_bags=False, --no-ps-fuse-bags: the unfused path, the same bits).
     The ring wraps round, so the chain is still open when training ends, with one step's bookkeeping planned ahead and never
     run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
@@ -470,8 +471,9 @@ def main():
                     help="--embedding cache, or --laia: the cache's planned flow (bookkeeping of the next batch beside "
                          "this step; --bsp 0: planned lookup + update pairs; --bsp -1, the default, with --cache lru: the planned "
                          "push-pull chain, one cache call per step, cache limit >= 2 * batch * 26; "
-                         "--model emb_sum_wdl at --bsp 0: the pairs are pooled -- the cache sums a sample's 26 rows as it "
-                         "reads them and takes the [batch, width] gradient as it is, no [batch * 26, width] tensor; "
+                         "--model emb_sum_wdl: the pairs, and the chain at --bsp -1 with --cache lru, are pooled -- the cache "
+                         "sums a sample's 26 rows as it reads them and takes the [batch, width] gradient as it is, no "
+                         "[batch * 26, width] tensor; "
                          "--laia: the update pushes the batch's push plan).  With --laia at world size > 1 it is "
                          "accepted and has no effect (the cache there talks to a remote store, call by call)")
     ap.add_argument("--no-ps-fuse-bags", action="store_true",

@@ -291,6 +291,8 @@ def _declare(L):
         "ha_cache_plan_block_push_pull": [vp, vp, c.c_int, vp, c.c_int, vp, vp],
         "ha_cache_push_pull_planned": [vp, i64, vp, i64, vp, vp],
         "ha_cache_run_planned_push_pulls": [vp, c.c_int, vp, vp, vp, vp, vp],
+        "ha_cache_push_pull_planned_bags": [vp, i64, i64, i64, vp, vp, i64, i64, i64, vp, vp, vp],
+        "ha_cache_run_planned_push_pulls_bags": [vp, c.c_int, i64, i64, i64, vp, vp, vp],
         "ha_cache_update": [vp, vp, c.c_int, i64, vp, vp],
         "ha_cache_update_same_keys": [vp, i64, vp, vp],
         "ha_cache_update_with_push_keys": [vp, vp, c.c_int, i64, vp, c.c_int, i64, vp, vp],

@@ -667,7 +667,8 @@ class _CacheBase:
     # ---- sum-pooled access in the planned flow (csrc/cache_block.hip): the [n, width] rows / gradients are never materialised
     def _pooled_due(self, who, lookup):
         if getattr(self, "_chain", None) or getattr(self, "_chain_last", None) is not None:
-            raise ValueError("%s: a planned push-pull chain is open: its steps are not pooled" % who)
+            raise ValueError("%s: a planned push-pull chain is open: its steps are not pooled by this call "
+                             "(embedding_push_pull_planned_bags)" % who)
         pl = getattr(self, "_planned", None)
         if not pl or pl[0][1] == lookup:
             raise ValueError("%s: %s" % (who, "no planned batch is due for its lookup" if lookup else
@@ -688,7 +689,7 @@ class _CacheBase:
             if bag < 1 or nbags * bag != n:
                 raise ValueError("%s: %d bags of %d ids are not the planned batch's %d ids" % (who, nbags, bag, n))
             return nbags
-        want_dtype, want_len = (torch.int64, nbags + 1) if ragged_name == "offsets" else (torch.int32, n)
+        want_dtype, want_len = (torch.int64, nbags + 1) if ragged_name.endswith("offsets") else (torch.int32, n)
         if not (torch.is_tensor(ragged) and ragged.is_cuda and ragged.dtype == want_dtype and ragged.is_contiguous() and
                 ragged.dim() == 1 and ragged.numel() == want_len):
             raise ValueError("%s: %s must be a contiguous %s device tensor [%d]" % (who, ragged_name, want_dtype, want_len))
@@ -755,6 +756,93 @@ class _CacheBase:
         check(self._L.ha_cache_run_planned_pairs_bags(self._h, cnt, n, nbags, int(bag), op, gp, ctypes.c_void_p(s.cuda_stream)),
               "ha_cache_run_planned_pairs_bags")
         del pl[:cnt]
+
+    # ---- the entries of a push-pull chain, sum-pooled on both sides ---------------------------------------------------------
+    def _chain_bags_args(self, who, j, out, bag_grads, bag, pull_offsets, push_bag_of):
+        """Entry j of the chain list, checked for a pooled call before anything native -> (kind, pull keys, push keys,
+        nbags_pull, nbags_push, bag of the pull side or None, bag of the push side or None)."""
+        chain = getattr(self, "_chain", None) or []
+        if j >= len(chain):
+            raise ValueError("%s: no entry of a planned push-pull chain is due (plan_block(..., push_pull=True))" % who)
+        kind, pull, push = chain[j]
+        has_pull, has_push = kind != "close", kind != "head"
+        if not has_pull and (out is not None or pull_offsets is not None):
+            raise ValueError("%s: the entry due closes the chain: it pulls nothing (out and pull_offsets must be None)" % who)
+        if not has_push and (bag_grads is not None or push_bag_of is not None):
+            raise ValueError("%s: the entry due is the chain's head: it pushes nothing (bag_grads and push_bag_of must be None)"
+                             % who)
+        if has_pull and out is None:
+            raise ValueError("%s: the entry due pulls a batch: out is missing" % who)
+        if has_push and bag_grads is None:
+            raise ValueError("%s: the entry due pushes the batch pulled before: bag_grads is missing" % who)
+        ragged = [r for r, there in ((pull_offsets, has_pull), (push_bag_of, has_push)) if there]
+        if bag is not None and all(r is not None for r in ragged):
+            raise ValueError("%s: give exactly one of bag and the ragged description per side: bag describes no side here" % who)
+        nbp = nbq = 0
+        bag_p = bag_q = None
+        if has_pull:
+            bag_p = bag if pull_offsets is None else None
+            nbp = self._pooled_args(who, "out", out, pull.numel(), bag_p, pull_offsets, "pull_offsets")
+        if has_push:
+            bag_q = bag if push_bag_of is None else None
+            nbq = self._pooled_args(who, "bag_grads", bag_grads, push.numel(), bag_q, push_bag_of, "push_bag_of")
+        return kind, pull, push, nbp, nbq, bag_p, bag_q
+
+    def embedding_push_pull_planned_bags(self, out, bag_grads, bag=None, pull_offsets=None, push_bag_of=None):
+        """The entry of the planned push-pull chain that is due, SUM-POOLED on both sides (ha_cache_push_pull_planned_bags): the
+        pooled gradient bag_grads [nbags, width] of the batch pulled by the entry before is accumulated and pushed
+        (embedding_update_planned_bags' launch), then the entry's own batch is pulled pooled into out [nbags, width]
+        (embedding_lookup_sum_planned's launch, judging staleness as a push-pull step must) -- bit for bit the unpooled entry
+        with ops.embedding_lookup_sum over its rows and the expanded gradient; no [n, width] tensor on either side.
+        The chain's head: bag_grads=None; its closing entry: out=None.  bag: fixed bags of `bag` ids, for every side that has no
+        ragged description; pull_offsets: int64 device tensor [nbags + 1] of the pull batch; push_bag_of: int32 device tensor
+        [n] of the push batch (ops.bag_of of the offsets it was pulled with).  Perf records and the wait handle: those of
+        embedding_lookup_planned (head), embedding_push_pull_planned (none) and embedding_update_planned (closing entry).
+        Pooled and unpooled entries may alternate within a chain."""
+        who = "embedding_push_pull_planned_bags"
+        kind, pull, push, nbp, nbq, bag_p, bag_q = self._chain_bags_args(who, 0, out, bag_grads, bag, pull_offsets, push_bag_of)
+        s = self._stream()
+        vp = ctypes.c_void_p
+        check(self._L.ha_cache_push_pull_planned_bags(
+            self._h, pull.numel() if pull is not None else -1, nbp, int(bag_p) if bag_p is not None else 0,
+            vp(pull_offsets.data_ptr() if pull_offsets is not None else None), vp(out.data_ptr() if nbp else None),
+            push.numel() if kind != "head" else 0, nbq, int(bag_q) if bag_q is not None else 0,
+            vp(push_bag_of.data_ptr() if push_bag_of is not None and push.numel() else None),
+            vp(bag_grads.data_ptr() if nbq else None), vp(s.cuda_stream)), "ha_cache_push_pull_planned_bags")
+        self._chain.pop(0)
+        if self.perf_enabled and kind != "step":
+            self._perf_record(0 if kind == "head" else 1)
+        return Wait(s, [pull, push, out, bag_grads, pull_offsets, push_bag_of]) if self._planned_waits else None
+
+    def run_planned_push_pulls_bags(self, outs, bag_grads, bag):
+        """The next len(outs) middle steps of the chain by ONE library call (ha_cache_run_planned_push_pulls_bags), pooled both
+        ways with fixed bags of `bag` ids: step k pulls into outs[k] [nbags, width] and pushes bag_grads[k] [nbags, width].
+        Every batch has the same number of ids.  For callers that have the gradient buffers at hand (a benchmark loop)."""
+        who = "run_planned_push_pulls_bags"
+        cnt = len(outs)
+        if len(bag_grads) != cnt:
+            raise ValueError("%s: %d outs, %d bag_grads" % (who, cnt, len(bag_grads)))
+        if cnt == 0:
+            return
+        if bag is None:
+            raise ValueError("%s: fixed bags only (bag is missing)" % who)
+        chain = getattr(self, "_chain", None) or []
+        if cnt > len(chain):
+            raise ValueError("%s: %d steps, but no entry of a planned push-pull chain is due after %d" % (who, cnt, len(chain)))
+        if any(e[0] != "step" for e in chain[:cnt]):
+            raise ValueError("%s: no push-pull step is due (the chain's head and its closing entry are made by "
+                             "embedding_push_pull_planned_bags)" % who)
+        kk = [self._chain_bags_args(who, j, outs[j], bag_grads[j], bag, None, None) for j in range(cnt)]
+        n, nbags = kk[0][1].numel(), kk[0][3]
+        if any(k[1].numel() != n or k[2].numel() != n for k in kk):
+            raise ValueError("%s: the steps of one call pull and push the same number of ids" % who)
+        s = self._stream()
+        op = (ctypes.c_void_p * cnt)(*[o.data_ptr() if nbags else None for o in outs])
+        gp = (ctypes.c_void_p * cnt)(*[g.data_ptr() if nbags else None for g in bag_grads])
+        check(self._L.ha_cache_run_planned_push_pulls_bags(self._h, cnt, n, nbags, int(bag), op, gp,
+                                                           ctypes.c_void_p(s.cuda_stream)),
+              "ha_cache_run_planned_push_pulls_bags")
+        del self._chain[:cnt]
 
     _planned_waits = True      # False: the planned calls return None instead of a wait handle (no event per call: bench loops)
 
@@ -1064,6 +1152,14 @@ class CacheSparseTable:
 
     def run_planned_push_pulls(self, dests, grads):
         self.cache.run_planned_push_pulls(dests, grads)
+
+    def embedding_push_pull_planned_bags(self, out, bag_grads, bag=None, pull_offsets=None, push_bag_of=None, sync=False):
+        w = self.cache.embedding_push_pull_planned_bags(out, bag_grads, bag=bag, pull_offsets=pull_offsets,
+                                                        push_bag_of=push_bag_of)
+        return self._finish(w, sync) if w is not None else None
+
+    def run_planned_push_pulls_bags(self, outs, bag_grads, bag):
+        self.cache.run_planned_push_pulls_bags(outs, bag_grads, bag)
 
     def embedding_lookup_planned(self, dest, sync=False):
         w = self.cache.embedding_lookup_planned(dest)

@@ -1113,6 +1113,9 @@ __global__ __launch_bounds__(1024) void cache_lookup_planned_kernel(
 // its own column slice, and the slice-0 wave of them stages the version.  (Bags of a batch are disjoint ranges of positions,
 // so that is one wave per slice.)
 // An item no bookkeeping launch wrote: sticky word 3 as in cache_lookup_planned_kernel, a zero row, nothing refreshed.
+// PP (the pooled pull half of a push-pull step, behind the step's push half): as cache_lookup_planned_kernel<.., PP> -- vadj[u]
+// is what the push half has just added to the version of a line it pushed; it is fetched beside the key's item, taken back for
+// the decision and added to the version staged for a pulled line.  PP = false reads nothing more than it did.
 template <int VEC>
 struct SumVec;
 template <>
@@ -1142,12 +1145,13 @@ struct SumPlan {
     const int32_t *perm;         // [n] occurrence index of sorted position p
     long long *pver;             // [n] staged versions, per sorted position (the heads')
     const PlanRec *rec;
+    const int32_t *vadj;         // PP only: per unique key, the version adjust (the chain slot's it_upd, see ChainArgs)
 };
 constexpr int kSumWaves = 4;     // waves per workgroup
 // row-pointer flags of a lane's occurrence
 constexpr int kSumOk = 1, kSumGrad = 2, kSumHead = 4;
 
-template <int VEC, int ROWS>
+template <int VEC, int ROWS, bool PP = false>
 __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_kernel(
     Cache c, SumPlan sp, long long n, long long bag, const int64_t *__restrict__ offsets, long long nbags, uint32_t nslice,
     float *__restrict__ out) {
@@ -1189,6 +1193,9 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
         const long long lk = static_cast<long long>(sp.uniq[uu]);
         int fl = sp.it_flag[uu];
         const int sg = sp.seg[uu];
+        long long adj = 0;
+        if (PP)
+            adj = static_cast<long long>(sp.vadj[uu]);
         if (fl & kPosVictim) {      // (LFU policies) the line this batch's own lookup evicts: still in its old slot
             s = static_cast<int>(sp.rec->vh_slot);
             fl = (fl & ~kPosInit) | ((fl & kPosVictimHg) ? kPosInit : 0);
@@ -1217,10 +1224,12 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
                 v = c.line[s].version;
             ho = sp.perm[sg];
         }
+        if (PP)      // the push half's commit is taken back for the decision (cache.cc:404 against :414-421)
+            v = v == -1 ? -1 : v - adj;
         const bool pull = is_miss || v == -1 || sv - v > c.pull_bound;
         const bool head = ok && mine && static_cast<long long>(ho) == j;
         if (head && sl == 0)
-            sp.pver[sg] = pull ? sv : kVerKeep;
+            sp.pver[sg] = pull ? sv + adj : kVerKeep;
         const uint64_t loff = static_cast<uint64_t>(ok ? s : 0) * width;      // float offset of the line's rows
         const float *src = ok ? (pull ? c.table + static_cast<uint64_t>(lk) * width : c.data + loff) : c.data;
         const uint64_t sa = reinterpret_cast<uint64_t>(src);
@@ -2209,10 +2218,64 @@ static int update_rows(ha_cache *h, hipStream_t s, void *ws, int64_t n, const fl
     return 0;
 }
 // ... of entry i of a chain block: the push half (the batch of the entry before)
-static int chain_push_rows(ha_cache *h, hipStream_t s, PlanSlot *sl, int i, const float *grads) {
+// (bag >= 1 or bag_of: `grads` is the pooled gradient of that batch)
+static int chain_push_rows(ha_cache *h, hipStream_t s, PlanSlot *sl, int i, const float *grads, int64_t bag = 0,
+                           const int32_t *bag_of = nullptr) {
     const long long at = static_cast<long long>(i) * h->c.nmax;
     return update_rows(h, s, sl->q_ws[i], sl->q_n[i], grads, sl->q_pos_item + at, sl->q_upd_pos + at, sl->q_pver[i],
-                       sl->q_ev_slot[i], sl->q_ev_key[i], sl->q_ev_upd[i], sl->q_rec[i], 0);
+                       sl->q_ev_slot[i], sl->q_ev_key[i], sl->q_ev_upd[i], sl->q_rec[i], 0, bag, bag_of);
+}
+
+// the launch shape of the pooled lookup: the slice of the 16-byte path by bag_sum_launch's rule (bagsum.hip) -> workgroups
+static uint64_t sum_blocks(const Cache &c, int64_t nbags, const float *out, int *vec_out, uint32_t *nslice_out) {
+    const int64_t width = c.width;
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(c.table) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    int vec = 1;
+    if (vec_ok)
+        for (vec = 4; vec > 1; vec >>= 1)
+            if (kWave * vec <= width && nbags * ((width + kWave * vec - 1) / (kWave * vec)) >= 2048)
+                break;
+    const uint32_t nslice = static_cast<uint32_t>((width + kWave * vec - 1) / (kWave * vec));
+    *vec_out = vec;
+    *nslice_out = nslice;
+    return (static_cast<uint64_t>(nbags) * nslice + kSumWaves - 1) / kSumWaves;
+}
+
+// the row launch of a planned lookup delivered sum-pooled (entry i of the slot) / of a chain step's pooled pull half (pp)
+static int lookup_sum_rows(ha_cache *h, hipStream_t s, PlanSlot *sl, int i, int64_t n, int64_t nbags, int64_t bag,
+                           const int64_t *offsets, float *out, bool pp, const char *who) {
+    Cache &c = h->c;
+    const long long at = static_cast<long long>(i) * c.nmax;
+    PlanPtrs p = plan_layout(sl->ws[i], n);
+    SumPlan sp{sl->it_slot + at, sl->it_flag + at, p.uniq, p.inverse, p.seg, p.perm, sl->pver + at, sl->rec + i,
+               pp ? sl->it_upd + at : nullptr};
+    int vec = 1;
+    uint32_t nslice = 1;
+    const uint64_t blocks64 = sum_blocks(c, nbags, out, &vec, &nslice);
+    HA_REQUIRE(blocks64 < (1ull << 31), "%s: batch too large", who);
+    const int64_t mean = offsets ? (n + nbags - 1) / nbags : bag;
+    const bool few = mean <= 8;
+    const dim3 grid(static_cast<unsigned>(blocks64)), block(kSumWaves * kWave);
+#define HA_SUM_CASE(V, R)                                                                                                    \
+    do {                                                                                                                     \
+        if (pp)                                                                                                              \
+            hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R, true>), grid, block, 0, s, c, sp, (long long)n,        \
+                               (long long)bag, offsets, (long long)nbags, nslice, out);                                      \
+        else                                                                                                                 \
+            hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R, false>), grid, block, 0, s, c, sp, (long long)n,       \
+                               (long long)bag, offsets, (long long)nbags, nslice, out);                                      \
+    } while (0)
+    if (vec == 4) {
+        if (few) HA_SUM_CASE(4, 8); else HA_SUM_CASE(4, 32);
+    } else if (vec == 2) {
+        if (few) HA_SUM_CASE(2, 8); else HA_SUM_CASE(2, 32);
+    } else {
+        if (few) HA_SUM_CASE(1, 8); else HA_SUM_CASE(1, 32);
+    }
+#undef HA_SUM_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int ha_cache_lookup_planned(ha_cache *h, int64_t n, float *dest, ha_stream_t stream) {
@@ -2286,50 +2349,20 @@ extern "C" int ha_cache_lookup_sum_planned(ha_cache *h, int64_t n, int64_t nbags
     int i = 0;
     PlanSlot *sl = plan_current(h, 0, &i);
     HA_REQUIRE(sl == nullptr || !sl->pp, "cache_lookup_sum_planned: the planned block is a push-pull chain (ha_cache_plan_block_push_pull): "
-               "its steps are not pooled -- ha_cache_lookup_planned / ha_cache_push_pull_planned and a pooling pass of the caller's");
-    HA_REQUIRE(!h->chain_open, "cache_lookup_sum_planned: a planned push-pull chain is open: its steps are not pooled");
+               "its steps are not pooled by this call -- ha_cache_push_pull_planned_bags serves the chain's entries pooled");
+    HA_REQUIRE(!h->chain_open, "cache_lookup_sum_planned: a planned push-pull chain is open: its steps are not pooled by this call "
+               "(ha_cache_push_pull_planned_bags)");
     HA_REQUIRE(sl != nullptr, "cache_lookup_sum_planned: no planned batch is due for its lookup (ha_cache_plan_block; lookup and "
                "update alternate)");
     HA_REQUIRE(sl->n[i] == n, "cache_lookup_sum_planned: the planned batch has %ld keys (got %ld)", (long)sl->n[i], (long)n);
-    Cache &c = h->c;
     hipStream_t s = as_stream(stream);
     if (!sl->waited) {
         HA_CHECK_HIP(hipStreamWaitEvent(s, sl->booked, 0));
         sl->waited = true;
     }
     cache_mark(h, kTStart, s, true);
-    if (nbags > 0) {
-        const long long at = static_cast<long long>(i) * c.nmax;
-        PlanPtrs p = plan_layout(sl->ws[i], n);
-        SumPlan sp{sl->it_slot + at, sl->it_flag + at, p.uniq, p.inverse, p.seg, p.perm, sl->pver + at, sl->rec + i};
-        const int64_t width = c.width;
-        const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(c.table) % 16 == 0) &&
-                            (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-        // the slice of the 16-byte path: bag_sum_launch's rule (bagsum.hip)
-        int vec = 1;
-        if (vec_ok)
-            for (vec = 4; vec > 1; vec >>= 1)
-                if (kWave * vec <= width && nbags * ((width + kWave * vec - 1) / (kWave * vec)) >= 2048)
-                    break;
-        const uint32_t nslice = static_cast<uint32_t>((width + kWave * vec - 1) / (kWave * vec));
-        const uint64_t blocks64 = (static_cast<uint64_t>(nbags) * nslice + kSumWaves - 1) / kSumWaves;
-        HA_REQUIRE(blocks64 < (1ull << 31), "cache_lookup_sum_planned: batch too large");
-        const int64_t mean = offsets ? (n + nbags - 1) / nbags : bag;
-        const bool few = mean <= 8;
-        const dim3 grid(static_cast<unsigned>(blocks64)), block(kSumWaves * kWave);
-#define HA_SUM_CASE(V, R)                                                                                                     \
-    hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R>), grid, block, 0, s, c, sp, (long long)n, (long long)bag, offsets, \
-                       (long long)nbags, nslice, out)
-        if (vec == 4) {
-            if (few) HA_SUM_CASE(4, 8); else HA_SUM_CASE(4, 32);
-        } else if (vec == 2) {
-            if (few) HA_SUM_CASE(2, 8); else HA_SUM_CASE(2, 32);
-        } else {
-            if (few) HA_SUM_CASE(1, 8); else HA_SUM_CASE(1, 32);
-        }
-#undef HA_SUM_CASE
-        HA_LAUNCH_CHECK();
-    }
+    if (nbags > 0 && lookup_sum_rows(h, s, sl, i, n, nbags, bag, offsets, out, false, "cache_lookup_sum_planned"))
+        return -1;
     cache_mark(h, kTEnd, s);
     h->settle_slot = nullptr;
     h->settle_idx = i;
@@ -2353,8 +2386,10 @@ extern "C" int ha_cache_update_planned_bags(ha_cache *h, int64_t n, const float 
     int i = 0;
     PlanSlot *sl = plan_current(h, 1, &i);
     HA_REQUIRE(sl == nullptr || !sl->pp, "cache_update_planned_bags: the planned block is a push-pull chain "
-               "(ha_cache_plan_block_push_pull): its steps are not pooled -- ha_cache_update_planned with the expanded gradient");
-    HA_REQUIRE(!h->chain_open, "cache_update_planned_bags: a planned push-pull chain is open: its steps are not pooled");
+               "(ha_cache_plan_block_push_pull): its steps are not pooled by this call -- ha_cache_push_pull_planned_bags serves the "
+               "chain's entries pooled");
+    HA_REQUIRE(!h->chain_open, "cache_update_planned_bags: a planned push-pull chain is open: its steps are not pooled by this call "
+               "(ha_cache_push_pull_planned_bags)");
     HA_REQUIRE(sl != nullptr, "cache_update_planned_bags: no planned batch is due for its update (its lookup comes first)");
     HA_REQUIRE(sl->n[i] == n, "cache_update_planned_bags: the planned batch has %ld keys (got %ld)", (long)sl->n[i], (long)n);
     Cache &c = h->c;
@@ -2411,6 +2446,103 @@ extern "C" int ha_cache_run_planned_push_pulls(ha_cache *h, int count, const int
     HA_REQUIRE(h && count >= 0 && (count == 0 || (n_pull && dests && n_push && grads)), "cache_run_planned_push_pulls: bad arguments");
     for (int k = 0; k < count; ++k)
         if (ha_cache_push_pull_planned(h, n_pull[k], dests[k], n_push[k], grads[k], stream))
+            return -1;
+    return 0;
+}
+
+// The entry of a push-pull chain that is due, POOLED on both sides: the head (a pooled plain lookup), a middle step (the push
+// half from the pooled gradient of the batch pulled by the step before -- cache_update_planned_kernel<.., BAGS> --, then the
+// pooled pull half, cache_lookup_sum_planned_kernel<.., PP>), or the closing entry (the push half alone).  It takes the place of
+// ha_cache_lookup_planned / ha_cache_push_pull_planned / ha_cache_update_planned in the chain's call sequence and leaves the
+// host state those leave; everything is checked before anything is enqueued.
+extern "C" int ha_cache_push_pull_planned_bags(ha_cache *h, int64_t n_pull, int64_t nbags_pull, int64_t bag_pull,
+                                               const int64_t *offsets_pull, float *out, int64_t n_push, int64_t nbags_push,
+                                               int64_t bag_push, const int32_t *bag_of_push, const float *bag_grads,
+                                               ha_stream_t stream) {
+    HA_REQUIRE(h, "cache_push_pull_planned_bags: null handle");
+    PlanSlot *sl = nullptr;
+    int i = 0;
+    for (int k = 0; k < ha_cache::kPlanSlots && sl == nullptr; ++k) {         // the older block first (as plan_current)
+        PlanSlot &q = h->plan[(h->plan_next + k) % ha_cache::kPlanSlots];
+        if (q.count > 0 && q.next_call < q.total())
+            sl = &q;
+    }
+    HA_REQUIRE(sl != nullptr, "cache_push_pull_planned_bags: no entry of a push-pull chain is due (ha_cache_plan_block_push_pull)");
+    HA_REQUIRE(sl->pp, "cache_push_pull_planned_bags: the planned block is a block of lookup + update pairs (ha_cache_plan_block): "
+               "its pooled calls are ha_cache_lookup_sum_planned / ha_cache_update_planned_bags");
+    i = sl->next_call;
+    const int kind = sl->kind[i];
+    const bool has_pull = kind != kChainClose, has_push = kind != kChainHead;
+    if (has_pull) {
+        HA_REQUIRE(n_pull >= 0 && nbags_pull >= 0 && nbags_pull < (1ll << 31) && bag_pull >= 0,
+                   "cache_push_pull_planned_bags: the entry due pulls a batch; bad pull sizes n=%ld nbags=%ld bag=%ld", (long)n_pull,
+                   (long)nbags_pull, (long)bag_pull);
+        HA_REQUIRE((bag_pull >= 1) != (offsets_pull != nullptr), "cache_push_pull_planned_bags: pull side: give exactly one of "
+                   "bag >= 1 and offsets (bag=%ld, offsets %s)", (long)bag_pull, offsets_pull ? "given" : "null");
+        HA_REQUIRE(offsets_pull != nullptr || (n_pull % bag_pull == 0 && n_pull / bag_pull == nbags_pull),
+                   "cache_push_pull_planned_bags: pull side: n=%ld is not nbags=%ld bags of bag=%ld ids", (long)n_pull,
+                   (long)nbags_pull, (long)bag_pull);
+        HA_REQUIRE(n_pull == 0 || nbags_pull >= 1, "cache_push_pull_planned_bags: pull side: %ld ids in no bag", (long)n_pull);
+        HA_REQUIRE(nbags_pull == 0 || out, "cache_push_pull_planned_bags: null output");
+        HA_REQUIRE(sl->n[i] == n_pull, "cache_push_pull_planned_bags: the planned entry pulls %ld keys (got %ld)", (long)sl->n[i],
+                   (long)n_pull);
+    } else {
+        HA_REQUIRE(n_pull == -1 && nbags_pull == 0 && bag_pull == 0 && !offsets_pull && !out,
+                   "cache_push_pull_planned_bags: the entry due closes the chain: it pulls nothing (n_pull == -1, pull arguments 0 / "
+                   "null)");
+    }
+    if (has_push) {
+        HA_REQUIRE(n_push >= 0 && nbags_push >= 0 && nbags_push < (1ll << 31) && bag_push >= 0 && bag_push < (1ll << 31),
+                   "cache_push_pull_planned_bags: bad push sizes n=%ld nbags=%ld bag=%ld", (long)n_push, (long)nbags_push,
+                   (long)bag_push);
+        // (an empty batch of ragged bags has no bag_of to give: neither is accepted then)
+        HA_REQUIRE(n_push == 0 ? !(bag_push >= 1 && bag_of_push != nullptr) : (bag_push >= 1) != (bag_of_push != nullptr),
+                   "cache_push_pull_planned_bags: push side: give exactly one of bag >= 1 and bag_of (bag=%ld, bag_of %s)",
+                   (long)bag_push, bag_of_push ? "given" : "null");
+        HA_REQUIRE(bag_push < 1 || (n_push % bag_push == 0 && n_push / bag_push == nbags_push),
+                   "cache_push_pull_planned_bags: push side: n=%ld is not nbags=%ld bags of bag=%ld ids", (long)n_push,
+                   (long)nbags_push, (long)bag_push);
+        HA_REQUIRE(n_push == 0 || (nbags_push >= 1 && bag_grads), "cache_push_pull_planned_bags: push side: %ld ids, but no bags or "
+                   "no gradient", (long)n_push);
+        HA_REQUIRE(sl->q_n[i] == n_push, "cache_push_pull_planned_bags: the planned entry pushes %ld keys (got %ld)", (long)sl->q_n[i],
+                   (long)n_push);
+    } else {
+        HA_REQUIRE(n_push == 0 && nbags_push == 0 && bag_push == 0 && !bag_of_push && !bag_grads,
+                   "cache_push_pull_planned_bags: the entry due is the chain's head: it pushes nothing (push arguments 0 / null)");
+    }
+    Cache &c = h->c;
+    if (has_pull && nbags_pull > 0) {
+        int vec = 1;
+        uint32_t nslice = 1;
+        HA_REQUIRE(sum_blocks(c, nbags_pull, out, &vec, &nslice) < (1ull << 31), "cache_push_pull_planned_bags: batch too large");
+    }
+    hipStream_t s = as_stream(stream);
+    if (!sl->waited) {
+        HA_CHECK_HIP(hipStreamWaitEvent(s, sl->booked, 0));
+        sl->waited = true;
+    }
+    cache_mark(h, kTStart, s, true);
+    if (has_push && n_push > 0 && chain_push_rows(h, s, sl, i, bag_grads, bag_of_push ? 0 : bag_push, bag_of_push))
+        return -1;
+    if (kind == kChainStep)
+        cache_mark(h, kTCopy, s);
+    if (has_pull && nbags_pull > 0 &&
+        lookup_sum_rows(h, s, sl, i, n_pull, nbags_pull, bag_pull, offsets_pull, out, kind == kChainStep, "cache_push_pull_planned_bags"))
+        return -1;
+    cache_mark(h, kTEnd, s);
+    h->settle_slot = has_pull ? sl : nullptr;
+    h->settle_idx = i;
+    if (!has_pull)
+        h->evict_empty = true;
+    return plan_called(h, sl, i, kind == kChainHead ? 0 : kind == kChainClose ? 1 : 2, s);
+}
+
+// `count` middle steps by ONE call, pooled both ways with fixed bags of `bag` ids: every step pulls and pushes n ids
+extern "C" int ha_cache_run_planned_push_pulls_bags(ha_cache *h, int count, int64_t n, int64_t nbags, int64_t bag,
+                                                    float *const *outs, const float *const *bag_grads, ha_stream_t stream) {
+    HA_REQUIRE(h && count >= 0 && (count == 0 || (outs && bag_grads)), "cache_run_planned_push_pulls_bags: bad arguments");
+    for (int k = 0; k < count; ++k)
+        if (ha_cache_push_pull_planned_bags(h, n, nbags, bag, nullptr, outs[k], n, nbags, bag, nullptr, bag_grads[k], stream))
             return -1;
     return 0;
 }

@@ -13,7 +13,8 @@ Mirrors (paths relative to /root/reference):
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
 cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and three switches of this build: cache_plan_ahead (the cache's
-planned flow), cache_fuse_bags (with it, at bsp 0: a sum-pooled lookup is pulled and pushed pooled, see Config) and
+planned flow), cache_fuse_bags (with it, at bsp 0 and on the LRU asp chain: a sum-pooled lookup is pulled and pushed pooled, see
+Config) and
 ps_fuse_bags (the same on the plain PS flavour, every schedule).  The data loader contract is the reference's
 `get_arr` / `get_next_arr` (python/hetu/dataloader.py:63-98): `next_ids()` returns the ids of the batch
 after the current one.  Everything computed goes through libherald_amd.so.
@@ -40,8 +41,10 @@ class Config:
         # not a HetuConfig field either: with cache_plan_ahead at bsp 0 (the planned pairs), a communicate op that was told the
         # bag size of a sum-pooled lookup (ParameterServerCommunicateOp(..., bag=F)) pulls [B, width] pooled rows
         # (embedding_lookup_sum_planned) and pushes the pooled gradient as it is (embedding_update_planned_bags): no [n, width]
-        # tensor on either side, the same bits.  False: the unfused path (per-occurrence rows, a summing pass, the expanded
-        # gradient).  Every other schedule -- the asp chain, ssp, no prefetch, world > 1, the call-by-call cache -- is unfused.
+        # tensor on either side, the same bits.  The planned push-pull chain of the asp-prefetch schedule (bsp < 0, LRU) is
+        # fused the same way: its head, every step and its last pull are embedding_push_pull_planned_bags.  False: the unfused
+        # path (per-occurrence rows, a summing pass, the expanded gradient).  Every other schedule -- ssp, no prefetch,
+        # world > 1, the call-by-call cache (LFU / LFUOpt at bsp < 0 included), laia push plans in a chain -- is unfused.
         self.cache_fuse_bags = cache_fuse_bags
         # the same switch for the plain PS flavour (no cstable_policy; ssp, asp and no prefetch alike): a communicate op that
         # was told its bag size pulls pooled rows (ShardedEmbedding.pull_sum) and pushes the pooled gradient (push_bags), and
@@ -141,7 +144,8 @@ class EmbeddingLookUpSum(EmbeddingLookUp):
     offsets[B + 1] for ragged bags.  With a device table it is the fused kernel (ops.embedding_lookup_sum).  On the PS, cache
     and prefetched paths the per-occurrence rows arrive as EmbeddingLookUp delivers them and the same kernel sums them, in the
     same position order, out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Two of those
-    paths are fused as well: the cache's planned pairs (Config.cache_fuse_bags) and the plain PS flavour
+    paths are fused as well: the cache's planned flow -- the pairs at bsp 0 and the LRU push-pull chain of the asp schedule
+    (Config.cache_fuse_bags) -- and the plain PS flavour
     (Config.ps_fuse_bags) -- with prefetch the communicate op's buffer already holds the pooled rows (the cache, or the
     sharded store's pull_sum, summed them as it read them) and is copied as it is; without prefetch the rows come from
     store.pull_sum directly, ragged bags included, whether or not the communicate op was told a bag size (`stream` is not
@@ -328,9 +332,10 @@ class ParameterServerCommunicateOp:
         """peek_ids(j) (optional, Config.cache_plan_ahead): the ids of the batch j batches after the one next_ids() returns
         (peek_ids(0) = that batch itself), without advancing the loader; None when there is none.
         bag (optional): the embedding is read through a sum-pooled lookup (EmbeddingLookUpSum) with fixed bags of `bag` ids --
-        ids arrive as [B, bag].  With the cache's planned pairs and Config.cache_fuse_bags, or on the plain PS flavour with
-        Config.ps_fuse_bags, the op then keeps sparse_pull_val as [B, width] and moves pooled rows and pooled gradients only;
-        on every other path (the call-by-call cache, the asp chain, the cache over a sharded store) it changes nothing.
+        ids arrive as [B, bag].  With the cache's planned flow (the pairs at bsp 0, the LRU push-pull chain of the asp schedule)
+        and Config.cache_fuse_bags, or on the plain PS flavour with Config.ps_fuse_bags, the op then keeps sparse_pull_val as
+        [B, width] and moves pooled rows and pooled gradients only; on every other path (the call-by-call cache, a chain with
+        laia push plans, the cache over a sharded store) it changes nothing.
         Without bag= the op's pulls and pushes are per occurrence as they always were; the lookup without prefetch
         (EmbeddingLookUpSum -> store.pull_sum) does not pass through this op and follows Config.ps_fuse_bags alone."""
         self.parameter = parameter
@@ -390,6 +395,8 @@ class ParameterServerCommunicateOp:
                     # every step is ONE cache call, push_pull(pull = batch k + 1, push = batch k): the planned push-pull chain
                     # (LRU; LFU / LFUOpt keep the call-by-call embedding_push_pull)
                     self._planned, self._chain = [], True
+                    if self.bag is not None and getattr(config, "cache_fuse_bags", True):
+                        self._bag = self.bag      # ... with pooled entries: embedding_push_pull_planned_bags
             else:
                 self.compute = self._compute_no_prefetch
         else:
@@ -429,7 +436,8 @@ class ParameterServerCommunicateOp:
         """Pooled slices (the gradient of EmbeddingLookUpSum: one row per bag) are expanded to per-occurrence values before
         they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The call-by-call
         cache and the step engines are NOT fused for pooled access: they move the expanded [n, width] values as they always
-        did.  The cache's planned pairs (Config.cache_fuse_bags) and the plain PS flavour (Config.ps_fuse_bags) are: slices
+        did.  The cache's planned flow -- pairs and the asp chain -- (Config.cache_fuse_bags) and the plain PS flavour
+        (Config.ps_fuse_bags) are: slices
         pooled by the op's own bag size stay [B, width] -- on the PS flavour ragged slices that carry their offsets too --;
         -lr is applied to those rows only, which is the same product for every occurrence of a bag."""
         if not getattr(grad, "pooled", False):
@@ -525,6 +533,8 @@ class ParameterServerCommunicateOp:
             nxt = self.peek_ids(self._peek_offset)
             if nxt is not None:
                 self._plan_chain(nxt)
+            if self._bag is not None:                              # dest is [B, width]: the head, pooled
+                return self.cache.embedding_push_pull_planned_bags(dest, None, bag=self._bag)
             return self.cache.embedding_lookup_planned(dest)
         if self._planned is not None:
             if not self._planned:                                  # the first pull: nothing planned yet
@@ -562,6 +572,10 @@ class ParameterServerCommunicateOp:
         if not self._planned or not _same_tensor(self._planned[0], grad.indices.reshape(-1)):
             raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp): the gradients pushed are not those of the "
                                "batch pulled last")
+        if self._bag is not None and not (getattr(grad, "pooled", False) and grad.bag == self._bag):
+            raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead, asp, bag=%d): the pull buffer holds pooled rows, "
+                               "so the gradients must be the pooled slices of EmbeddingLookUpSum_Gradient over bags of %d ids; "
+                               "use cache_fuse_bags=False for per-occurrence gradients" % (self._bag, self._bag))
         nxt = self.next_ids()
         if len(self._planned) < 2:                                 # peek_ids had run dry: the step is planned now
             self._plan_chain(nxt)
@@ -573,6 +587,9 @@ class ParameterServerCommunicateOp:
             self._plan_chain(after)
         self._planned.pop(0)
         width = self.parameter.shape[1]
+        if self._bag is not None:      # (checked above, before anything was planned: the slices are pooled by this bag size)
+            return self.cache.embedding_push_pull_planned_bags(self.sparse_pull_val.reshape(-1, width),
+                                                               grad.values.reshape(-1, width).contiguous(), bag=self._bag)
         return self.cache.embedding_push_pull_planned(self.sparse_pull_val.reshape(-1, width),
                                                       grad.values.reshape(-1, width).contiguous())
 

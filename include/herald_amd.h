@@ -998,8 +998,9 @@ int ha_cache_run_planned_pairs(ha_cache *cache, int count, const int64_t *n, flo
  * gradient expanded to [n, width], in bound mode and in push-key mode; it takes that call's place in the sequence.
  *
  * The state either pooled call leaves is the state its unpooled counterpart leaves, so a pooled lookup may be followed by an
- * unpooled update and the other way round.  The steps of a push-pull chain (ha_cache_plan_block_push_pull) are not pooled:
- * both calls refuse such a block, and an open chain, before anything is enqueued. */
+ * unpooled update and the other way round.  The steps of a push-pull chain (ha_cache_plan_block_push_pull) are not pooled by
+ * these two calls: both refuse such a block, and an open chain, before anything is enqueued -- a chain's pooled entries are
+ * ha_cache_push_pull_planned_bags. */
 int ha_cache_lookup_sum_planned(ha_cache *cache, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
                                 ha_stream_t stream);
 int ha_cache_update_planned_bags(ha_cache *cache, int64_t n, const float *bag_grads, int64_t nbags, int64_t bag,
@@ -1040,6 +1041,31 @@ int ha_cache_push_pull_planned(ha_cache *cache, int64_t n_pull, float *dest, int
 /* `count` middle steps of a chain by one call: ha_cache_push_pull_planned(n_pull[k], dests[k], n_push[k], grads[k]) */
 int ha_cache_run_planned_push_pulls(ha_cache *cache, int count, const int64_t *n_pull, float *const *dests,
                                     const int64_t *n_push, const float *const *grads, ha_stream_t stream);
+/* The entries of a push-pull chain, SUM-POOLED on both sides (csrc/cache_block.hip): what the emb_sum_* models need of the
+ * asp-with-prefetch schedule, without the [n, width] rows of the pull and without the expanded gradient of the push.
+ * ha_cache_push_pull_planned_bags serves whichever entry of the chain block is due:
+ *   the HEAD          n_push == 0, every push argument 0 / NULL: ha_cache_lookup_sum_planned's launch (one ha_cache_perf record,
+ *                     as ha_cache_lookup_planned leaves for a head);
+ *   a MIDDLE step     both sides: the push half reads bag_grads[nbags_push, width] -- the pooled gradient of the batch pulled by
+ *                     the entry before -- as ha_cache_update_planned_bags does, then the pull half delivers the step's own batch
+ *                     pooled into out[nbags_pull, width], judging staleness with the line's version as it was before the push
+ *                     half's commit, as ha_cache_push_pull_planned does.  Two launches, no perf record;
+ *   the CLOSING entry n_pull == -1, every pull argument 0 / NULL: the push half alone (one perf record, as
+ *                     ha_cache_update_planned leaves for a closing entry).
+ * Bags per side as in the pooled pair calls: exactly one of bag >= 1 (n == nbags * bag) and the ragged description -- device
+ * int64 offsets_pull[nbags_pull + 1] (clamped as ha_cache_lookup_sum_planned clamps them), device int32 bag_of_push[n_push]
+ * (ha_bag_of) -- with the argument checks of ha_cache_lookup_sum_planned / ha_cache_update_planned_bags.  Every check is made
+ * before anything is enqueued and before the block's call counter moves; a block of pairs, or no chain entry due, is refused.
+ * Bit for bit the unpooled entry followed by ha_gather_sum over the ids 0 .. n-1 / fed the expanded gradient, and the same
+ * state of cache, store and host: pooled and unpooled entries may alternate freely within one chain.  The pooled pair calls
+ * above keep refusing a chain. */
+int ha_cache_push_pull_planned_bags(ha_cache *cache, int64_t n_pull, int64_t nbags_pull, int64_t bag_pull,
+                                    const int64_t *offsets_pull, float *out, int64_t n_push, int64_t nbags_push, int64_t bag_push,
+                                    const int32_t *bag_of_push, const float *bag_grads, ha_stream_t stream);
+/* `count` middle steps of n ids in fixed bags by one call: ha_cache_push_pull_planned_bags(n, nbags, bag, NULL, outs[k], n, nbags,
+ * bag, NULL, bag_grads[k]) */
+int ha_cache_run_planned_push_pulls_bags(ha_cache *cache, int count, int64_t n, int64_t nbags, int64_t bag, float *const *outs,
+                                         const float *const *bag_grads, ha_stream_t stream);
 int ha_cache_update(ha_cache *cache, const void *keys, int key_kind, int64_t n,
                     const float *grads, ha_stream_t stream);
 /* ha_cache_update for the key batch of the immediately preceding ha_cache_lookup on this cache (the
