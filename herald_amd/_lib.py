@@ -189,6 +189,13 @@ def _declare(L):
         "ha_shard_step_push": [vp, i64, i64, vp, vp, vp, i64, vp, vp, f32, vp],
         "ha_shard_step": [vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, f32, vp],
         "ha_shard_steps": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, f32, vp],
+        "ha_gather2_sum_u32map": [vp, i64, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp],
+        "ha_apply_mapped_bags": [vp, i64, i64, vp, i64, vp, f32, vp, i64, vp, vp, vp],
+        "ha_push_apply_scaled_bags_finished": [vp, i64, i64, vp, i64, vp, i64, vp, f32, vp],
+        "ha_shard_step_pull_sum": [vp, i64, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp],
+        "ha_shard_step_push_bags": [vp, i64, i64, vp, vp, vp, i64, vp, vp, i64, i64, vp, f32, vp],
+        "ha_shard_step_bags": [vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, f32, vp],
+        "ha_shard_steps_bags": [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, f32, vp],
         "ha_qapply_steps_sync": [vp, i64, i64, f32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "ha_qapply_steps_counts": [vp, i64, i64, f32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "ha_qapply_geometry": [i64, i64, i64, i64, i64, vp, vp],

@@ -113,6 +113,78 @@ __global__ __launch_bounds__(kBagWaves *kWave) void bag_sum_kernel(
         __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
 }
 
+// The same sum over TWO sources (the sized expand of the sharded step, ha_gather2_u32map, fused with the sum over each bag): lane
+// l holds the map word of position l of the block and forms the ADDRESS of its row -- table[map & 0x7FFFFFFF] if bit 31 is set
+// (a key of this rank's own shard), recv[map] otherwise (a row an owner sent); an index beyond its array is clamped to row 0 of
+// its array and adds a zero row (0xFFFFFFFF is one) -- and the address is what v_readlane broadcasts.  Everything else is
+// bag_sum_kernel's: one wave per (bag, column slice), ROWS branch-free loads in flight before the first add, the same chain.
+// The host gives a side without rows the other side's pointer, so the clamped loads always read memory that exists.
+template <int VEC, int ROWS>
+__global__ __launch_bounds__(kBagWaves *kWave) void bag_sum2_kernel(
+    const float *table, uint64_t rows, const float *recv, uint64_t recv_rows, uint32_t width, const uint32_t *__restrict__ map,
+    int64_t n, int64_t bag, const int64_t *__restrict__ offsets, int64_t nbags, uint32_t nslice, float *__restrict__ out) {
+    typedef typename BagVec<VEC>::T V;
+    const int lane = lane_id();
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kBagWaves + (threadIdx.x >> 6);   // wave-uniform
+    if (item >= static_cast<uint64_t>(nbags) * nslice)
+        return;
+    const int64_t b = static_cast<int64_t>(item / nslice);
+    const uint32_t sl = static_cast<uint32_t>(item - static_cast<uint64_t>(b) * nslice);
+    int64_t lo, hi;
+    if (offsets != nullptr) {
+        lo = offsets[b];
+        hi = offsets[b + 1];
+        lo = lo < 0 ? 0 : (lo > n ? n : lo);
+        hi = hi < lo ? lo : (hi > n ? n : hi);
+    } else {
+        lo = b * bag;
+        hi = lo + bag;      // (n == nbags * bag: checked by the host)
+    }
+    const uint32_t col = (sl * kWave + lane) * VEC;
+    const bool live = col < width;       // (VEC > 1: width % VEC == 0, so a live lane's VEC columns all exist)
+    const uint32_t lcol = live ? col : 0;
+    V acc;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+        BagVec<VEC>::set(acc, k, 0.f);
+    for (int64_t j0 = lo; j0 < hi; j0 += kWave) {
+        const int cnt = static_cast<int>(hi - j0 < kWave ? hi - j0 : kWave);      // positions of this block (wave-uniform)
+        const int64_t j = j0 + (lane < cnt ? lane : cnt - 1);                      // lo <= j < hi <= n
+        const uint32_t m = map[j];
+        const bool own = (m & 0x80000000u) != 0;
+        const uint64_t r = m & 0x7FFFFFFFu;
+        const bool ok = r < (own ? rows : recv_rows);
+        const unsigned long long okm = __ballot(ok);
+        const uint64_t src = reinterpret_cast<uint64_t>((own ? table : recv) + (ok ? r : 0) * width);
+        const int src_lo = static_cast<int>(static_cast<uint32_t>(src));
+        const int src_hi = static_cast<int>(static_cast<uint32_t>(src >> 32));
+        for (int c = 0; c < cnt; c += ROWS) {
+            V v[ROWS];
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const int tt = c + t < cnt ? c + t : cnt - 1;
+                const uint64_t a = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(src_hi, tt))) << 32) |
+                                   static_cast<uint32_t>(__builtin_amdgcn_readlane(src_lo, tt));
+                v[t] = *reinterpret_cast<const V *>(reinterpret_cast<const float *>(a) + lcol);
+            }
+            __builtin_amdgcn_sched_barrier(0);      // (as bag_sum_kernel: the whole round is requested before the first add)
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const bool in = c + t < cnt;                                  // wave-uniform
+                const bool rok = ((okm >> (in ? c + t : 0)) & 1ull) != 0;     // an index beyond its array adds a zero row
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float a = BagVec<VEC>::get(acc, k);
+                    const float s = __fadd_rn(a, rok ? BagVec<VEC>::get(v[t], k) : 0.f);
+                    BagVec<VEC>::set(acc, k, in ? s : a);
+                }
+            }
+        }
+    }
+    if (live)
+        __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
+}
+
 // bag_of[i] = the bag of occurrence i: the largest b in [0, nbags) with offsets[b] <= i (empty bags are skipped).  Always in
 // [0, nbags), whatever offsets holds; offsets[0] and offsets[nbags] are not read.
 __global__ __launch_bounds__(256) void bag_of_kernel(const int64_t *__restrict__ offsets, int nbags, int64_t n,
@@ -134,6 +206,39 @@ __global__ __launch_bounds__(256) void bag_of_kernel(const int64_t *__restrict__
 // Slice width of the 16-byte path in floats: 0 = by the rule in bag_sum_launch, else 64 / 128 / 256 (ha_debug_bag_slice).
 static int g_bag_slice = 0;
 
+// The launch rule of the bag sums (both kernels): column slice, grid and rows per round of a batch.
+struct BagLaunchRule {
+    int vec;
+    uint32_t nslice;
+    unsigned blocks;
+    bool few;
+};
+static int bag_launch_rule(const char *what, bool vec_ok, int64_t width, int64_t n, int64_t bag, const int64_t *offsets,
+                           int64_t nbags, BagLaunchRule *r) {
+    // Slice of the 16-byte path: the widest one that is no wider than a row and still gives the chip 8 waves per compute unit
+    // (2,048 waves); batches too small for that take 64-float slices.  (256 bags of 26 x 512 floats: 2,048 waves of 64 floats;
+    // 4,096 bags of 128 floats: 4,096 waves of 128 floats.  Not measured yet: docs/EXPERIMENTS.md round 6 section 18.)
+    int vec = 1;
+    if (vec_ok) {
+        if (g_bag_slice != 0) {
+            vec = g_bag_slice / kWave;
+        } else {
+            for (vec = 4; vec > 1; vec >>= 1)
+                if (kWave * vec <= width && nbags * ((width + kWave * vec - 1) / (kWave * vec)) >= 2048)
+                    break;
+        }
+    }
+    r->nslice = static_cast<uint32_t>((width + kWave * vec - 1) / (kWave * vec));
+    const uint64_t blocks64 = (static_cast<uint64_t>(nbags) * r->nslice + kBagWaves - 1) / kBagWaves;
+    HA_REQUIRE(blocks64 < (1ull << 31), "%s: batch too large", what);
+    // rows per round by the (mean) bag size: a bag of 26 is one round of 32 requests
+    const int64_t mean = offsets ? (n + nbags - 1) / nbags : bag;
+    r->few = mean <= 8;
+    r->blocks = static_cast<unsigned>(blocks64);
+    r->vec = vec;
+    return 0;
+}
+
 template <typename IdT>
 static int bag_sum_launch(const char *what, const float *table, int64_t rows, int64_t width, const IdT *ids, int64_t n,
                           int64_t bag, const int64_t *offsets, int64_t nbags, float *out, hipStream_t stream) {
@@ -154,26 +259,13 @@ static int bag_sum_launch(const char *what, const float *table, int64_t rows, in
     }
     const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
                         (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    // Slice of the 16-byte path: the widest one that is no wider than a row and still gives the chip 8 waves per compute unit
-    // (2,048 waves); batches too small for that take 64-float slices.  (256 bags of 26 x 512 floats: 2,048 waves of 64 floats;
-    // 4,096 bags of 128 floats: 4,096 waves of 128 floats.  Not measured yet: docs/EXPERIMENTS.md round 6 section 18.)
-    int vec = 1;
-    if (vec_ok) {
-        if (g_bag_slice != 0) {
-            vec = g_bag_slice / kWave;
-        } else {
-            for (vec = 4; vec > 1; vec >>= 1)
-                if (kWave * vec <= width && nbags * ((width + kWave * vec - 1) / (kWave * vec)) >= 2048)
-                    break;
-        }
-    }
-    const uint32_t nslice = static_cast<uint32_t>((width + kWave * vec - 1) / (kWave * vec));
-    const uint64_t blocks64 = (static_cast<uint64_t>(nbags) * nslice + kBagWaves - 1) / kBagWaves;
-    HA_REQUIRE(blocks64 < (1ull << 31), "%s: batch too large", what);
-    // rows per round by the (mean) bag size: a bag of 26 is one round of 32 requests
-    const int64_t mean = offsets ? (n + nbags - 1) / nbags : bag;
-    const bool few = mean <= 8;
-    const dim3 grid(static_cast<unsigned>(blocks64)), block(kBagWaves * kWave);
+    BagLaunchRule lr;
+    if (bag_launch_rule(what, vec_ok, width, n, bag, offsets, nbags, &lr))
+        return -1;
+    const int vec = lr.vec;
+    const uint32_t nslice = lr.nslice;
+    const bool few = lr.few;
+    const dim3 grid(lr.blocks), block(kBagWaves * kWave);
 #define HA_BAG_CASE(V, R)                                                                                               \
     hipLaunchKernelGGL((bag_sum_kernel<IdT, V, R>), grid, block, 0, stream, table, (uint64_t)rows, (uint32_t)width, ids, n, \
                        bag, offsets, nbags, nslice, out)
@@ -185,6 +277,50 @@ static int bag_sum_launch(const char *what, const float *table, int64_t rows, in
         if (few) HA_BAG_CASE(1, 8); else HA_BAG_CASE(1, 32);
     }
 #undef HA_BAG_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ha_gather2_sum_u32map: every check of bag_sum_launch and of ha_gather2_u32map, before any device access.
+static int bag_sum2_launch(const float *table, int64_t rows, const float *recv, int64_t recv_rows, int64_t width,
+                           const uint32_t *map, int64_t n, int64_t bag, const int64_t *offsets, int64_t nbags, float *out,
+                           hipStream_t stream) {
+    const char *what = "ha_gather2_sum_u32map";
+    HA_REQUIRE(rows >= 0 && recv_rows >= 0 && width >= 1 && width < (1ll << 30) && n >= 0 && nbags >= 0 && bag >= 0,
+               "%s: bad sizes rows=%ld recv_rows=%ld width=%ld n=%ld bag=%ld nbags=%ld", what, (long)rows, (long)recv_rows,
+               (long)width, (long)n, (long)bag, (long)nbags);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld, offsets %s)", what,
+               (long)bag, offsets ? "given" : "null");
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+               (long)n, (long)nbags, (long)bag);
+    if (nbags == 0)
+        return 0;
+    HA_REQUIRE(out != nullptr && (map != nullptr || n == 0) && (table != nullptr || rows == 0) &&
+                   (recv != nullptr || recv_rows == 0), "%s: null pointer", what);
+    // a side that has no rows is never dereferenced: its clamped loads read row 0 of the other side (and add zeros)
+    if (rows == 0) table = recv;
+    if (recv_rows == 0) recv = table;
+    if (rows == 0 && recv_rows == 0) {      // every index is beyond its array
+        HA_CHECK_HIP(hipMemsetAsync(out, 0, static_cast<size_t>(nbags) * width * sizeof(float), stream));
+        return 0;
+    }
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(recv) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    BagLaunchRule lr;
+    if (bag_launch_rule(what, vec_ok, width, n, bag, offsets, nbags, &lr))
+        return -1;
+    const dim3 grid(lr.blocks), block(kBagWaves * kWave);
+#define HA_BAG2_CASE(V, R)                                                                                              \
+    hipLaunchKernelGGL((bag_sum2_kernel<V, R>), grid, block, 0, stream, table, (uint64_t)rows, recv, (uint64_t)recv_rows, \
+                       (uint32_t)width, map, n, bag, offsets, nbags, lr.nslice, out)
+    if (lr.vec == 4) {
+        if (lr.few) HA_BAG2_CASE(4, 8); else HA_BAG2_CASE(4, 32);
+    } else if (lr.vec == 2) {
+        if (lr.few) HA_BAG2_CASE(2, 8); else HA_BAG2_CASE(2, 32);
+    } else {
+        if (lr.few) HA_BAG2_CASE(1, 8); else HA_BAG2_CASE(1, 32);
+    }
+#undef HA_BAG2_CASE
     HA_LAUNCH_CHECK();
     return 0;
 }
@@ -241,6 +377,14 @@ extern "C" int ha_gather_sum_u32keys(const float *rows_buf, int64_t rows, int64_
                                      int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream) {
     return ha::bag_sum_launch<uint32_t>("ha_gather_sum_u32keys", rows_buf, rows, width, keys, n, bag, offsets, nbags, out,
                                         ha::as_stream(stream));
+}
+
+// The sized expand of the sharded step and the sum over each bag in one pass: position i's row is the one ha_gather2_u32map
+// writes for it (own shard / received rows / zeros), out[b,:] the position-ordered chain over bag b (csrc/shard.hip).
+extern "C" int ha_gather2_sum_u32map(const float *table, int64_t rows, const float *recv, int64_t recv_rows, int64_t width,
+                                     const uint32_t *map, int64_t n, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                     float *out, ha_stream_t stream) {
+    return ha::bag_sum2_launch(table, rows, recv, recv_rows, width, map, n, bag, offsets, nbags, out, ha::as_stream(stream));
 }
 
 extern "C" int ha_bag_of(const int64_t *offsets, int64_t nbags, int64_t n, int32_t *bag_of, ha_stream_t stream) {

@@ -507,7 +507,14 @@ static int apply_launch(float *dst, int64_t dst_rows, int64_t width,
 
 // apply of a FINISHED plan by unique key (larger batches); plan scratch keys_alt holds the long list
 namespace ha {
-// BAGS: the kernels' BAGS instantiations (source rows through maps.valmap / maps.valdiv; kModeOpt and kModeReduce)
+// Tolerance mode 2: whether a plain launch of this size into `dst` cuts its long runs into chunks (the 16-byte path, at most four
+// slices).  The pooled entry points ask it too: there are no chunked bags, so where the expanded call would chunk they expand.
+static bool plain_launch_chunks(int tree_from, int64_t n, int64_t width, const void *dst) {
+    return g_tree_chunks && tree_from > 0 && n > kSmallMax && n <= kFinishChunkedMax && width % 4 == 0 &&
+           reinterpret_cast<uintptr_t>(dst) % 16 == 0 && (width + kWave - 1) / kWave <= 4;
+}
+// BAGS: the kernels' BAGS instantiations (source rows through maps.valmap / maps.valdiv; kModeSgd, kModePush, kModeOpt and
+// kModeReduce)
 template <int MODE, bool BAGS>
 static int apply_by_unique_impl(float *dst, int64_t dst_rows, int64_t width, void *plan_ws, int64_t n,
                                 const float *grads, float lr, hipStream_t stream, ApplyMaps maps) {
@@ -527,7 +534,7 @@ static int apply_by_unique_impl(float *dst, int64_t dst_rows, int64_t width, voi
         ChunkPlan cp{nullptr, nullptr, nullptr};
         const int nslice = static_cast<int>((width + kWave - 1) / kWave);
         const bool plain = !maps.rowmap && !maps.valmap && !maps.dst_init && MODE != kModeOpt && !BAGS;
-        if (g_tree_chunks && maps.tree_from > 0 && plain && vec_ok && nslice <= 4) {
+        if (plain && vec_ok && plain_launch_chunks(maps.tree_from, n, width, dst)) {
             static DeviceOnce lds_allowed;
             if (lds_allowed.run([]() -> int {
                     HA_ALLOW_LDS((apply_listed_kernel<MODE, 4, BAGS>), kListedLdsBytes);
@@ -888,12 +895,10 @@ extern "C" int ha_dedup_reduce_bags(const void *plan_ws, int64_t n, const float 
     hipStream_t s = as_stream(stream);
     const bool fixed = bag_of == nullptr;
     if (n > kSmallMax) {      // a FINISHED plan: waves map to unique keys
-        // tolerance mode 2 cuts the long runs of a plain launch into chunks (apply_by_unique_impl's own conditions: the 16-byte
-        // path, at most four slices; the expanded gradient would be aligned scratch); there are no chunked bags: expand, then
-        // that launch.  Where the expanded call would not chunk, the bag kernels below take the same trees as it does.
-        const bool would_chunk = g_tree_chunks && tolerance_tree_from() > 0 && n <= kFinishChunkedMax && width % 4 == 0 &&
-                                 reinterpret_cast<uintptr_t>(reduced) % 16 == 0 && (width + kWave - 1) / kWave <= 4;
-        if (would_chunk) {
+        // tolerance mode 2 cuts the long runs of a plain launch into chunks (the expanded gradient would be aligned scratch);
+        // there are no chunked bags: expand, then that launch.  Where the expanded call would not chunk, the bag kernels below
+        // take the same trees as it does.
+        if (plain_launch_chunks(tolerance_tree_from(), n, width, reduced)) {
             void *ws = nullptr;
             if (scratch_get(s, static_cast<size_t>(n) * width * sizeof(float), &ws))
                 return -1;
@@ -995,6 +1000,151 @@ extern "C" int ha_apply_mapped(float *dst, int64_t dst_rows, int64_t width,
     else
         hipLaunchKernelGGL((ha::apply_mapped_kernel<1>), dim3(blocks), dim3(1024), ha::kApplyLdsBytes, ha::as_stream(stream),
                            dst, (uint64_t)dst_rows, (int)width, v.sorted, v.perm, v.upos, (int)n, src, lr, maps);
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the pooled forms of ha_apply_mapped and ha_push_apply_scaled_finished (the sharded step on sum-pooled access) ----------
+// The same bodies in their BAGS instantiations: the source row of occurrence i is the row of its bag (i / bag in registers for
+// fixed bags -- no map read --, bag_of[i] for ragged ones), so the same runs take the same chain or tree over the same values
+// as the unpooled call on bag_grads expanded to [n, width]: the same bits, without the expanded tensor.
+namespace ha {
+template <int VEC, bool FIXED>
+__global__ __launch_bounds__(1024, 8) void apply_mapped_bags_kernel(
+    float *__restrict__ dst, uint64_t dst_rows, int width, const uint32_t *__restrict__ sorted,
+    const int32_t *__restrict__ perm, const int32_t *__restrict__ upos, int n, const float *__restrict__ bag_grads, float lr,
+    ApplyMaps maps) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
+    if (FIXED)
+        maps.valmap = nullptr;
+    else
+        maps.valdiv = 0;
+    apply_body<kModeSgd, VEC, false, kHandNone, true>(dst, dst_rows, width, sorted, perm, upos, n, bag_grads, lr, blockIdx.x,
+                                                      s_apply, nullptr, maps);
+}
+
+template <int VEC, bool FIXED>
+__global__ __launch_bounds__(1024, 8) void push_bags_kernel(
+    float *__restrict__ dst, uint64_t dst_rows, int width, const uint32_t *__restrict__ sorted,
+    const int32_t *__restrict__ perm, const int32_t *__restrict__ upos, int n, const float *__restrict__ bag_grads, float scale,
+    int tree_from, int bag, const int32_t *__restrict__ bag_of) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
+    ApplyMaps maps{};
+    maps.tree_from = tree_from;
+    maps.valmap = FIXED ? nullptr : bag_of;
+    maps.valdiv = FIXED ? bag : 0;
+    apply_body<kModePush, VEC, false, kHandNone, true>(dst, dst_rows, width, sorted, perm, upos, n, bag_grads, scale, blockIdx.x,
+                                                       s_apply, nullptr, maps);
+}
+
+// the argument rules the pooled applies share (ha_sgd_apply_bags's); everything here precedes any device access
+static int bags_args_ok(const char *what, int64_t rows, int64_t width, int64_t n, int64_t bag, const int32_t *bag_of) {
+    HA_REQUIRE(n >= 0 && rows >= 0 && width >= 1 && width < (1 << 30) && n < (1ll << 31) && bag >= 0, "%s: bad sizes", what);
+    HA_REQUIRE((bag >= 1) != (bag_of != nullptr), "%s: give exactly one of bag >= 1 and bag_of (bag=%ld)", what, (long)bag);
+    HA_REQUIRE(bag_of != nullptr || (bag < (1ll << 31) && n % bag == 0), "%s: n=%ld is not a multiple of bag=%ld", what, (long)n,
+               (long)bag);
+    return 0;
+}
+}  // namespace ha
+
+// ha_apply_mapped with src = bag_grads expanded to [n, width], without the expanded tensor:
+//   dst[rowmap[u],:] = (init ? dst[rowmap[u],:] : 0) - lr*bag_grads[bag of i0,:] - lr*bag_grads[bag of i1,:] ...
+// rowmap / dst_init may be NULL as there.  By sorted position, or by unique key where ha_apply_mapped goes by unique key.
+extern "C" int ha_apply_mapped_bags(float *dst, int64_t dst_rows, int64_t width, const void *plan_ws, int64_t n,
+                                    const float *bag_grads, float lr, const int32_t *rowmap, int64_t bag,
+                                    const int32_t *bag_of, const uint8_t *dst_init, ha_stream_t stream) {
+    using namespace ha;
+    if (bags_args_ok("ha_apply_mapped_bags", dst_rows, width, n, bag, bag_of))
+        return -1;
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(dst && plan_ws && bag_grads, "ha_apply_mapped_bags: null pointer");
+    const bool fixed = bag_of == nullptr;
+    ApplyMaps maps{rowmap, bag_of, dst_init, nullptr, nullptr};
+    maps.tree_from = tolerance_tree_from();
+    maps.valdiv = fixed ? static_cast<int>(bag) : 0;
+    ha_plan_view v;
+    if (ha_plan_view_of(const_cast<void *>(plan_ws), n, &v) != 0)
+        return -1;
+    if (rowmap != nullptr && n > kSmallMax && n <= kFinishChunkedMax && mapped_by_unique())
+        return apply_by_unique_impl<kModeSgd, true>(dst, dst_rows, width, const_cast<void *>(plan_ws), n, bag_grads, lr,
+                                                    as_stream(stream), maps);
+    const unsigned blocks = static_cast<unsigned>((n + kPosPerBlock - 1) / kPosPerBlock);
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(bag_grads) % 16 == 0);
+    static DeviceOnce lds_allowed;
+    if (lds_allowed.run([]() -> int {
+            HA_ALLOW_LDS((apply_mapped_bags_kernel<4, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_mapped_bags_kernel<4, false>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_mapped_bags_kernel<1, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_mapped_bags_kernel<1, false>), kApplyLdsBytes);
+            return 0;
+        }))
+        return -1;
+#define HA_MBAGS_CASE(V, F)                                                                                              \
+    hipLaunchKernelGGL((apply_mapped_bags_kernel<V, F>), dim3(blocks), dim3(1024), kApplyLdsBytes, as_stream(stream), dst, \
+                       (uint64_t)dst_rows, (int)width, v.sorted, v.perm, v.upos, (int)n, bag_grads, lr, maps)
+    if (vec_ok && fixed) HA_MBAGS_CASE(4, true);
+    else if (vec_ok) HA_MBAGS_CASE(4, false);
+    else if (fixed) HA_MBAGS_CASE(1, true);
+    else HA_MBAGS_CASE(1, false);
+#undef HA_MBAGS_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ha_push_apply_scaled_finished with grads = bag_grads expanded to [n, width], without the expanded tensor (a FINISHED plan):
+// by sorted position up to 36,864 ids, by unique key beyond.  Tolerance mode 2: where the expanded call would cut long runs into
+// chunks there are no chunked bags -- expand into the per-stream scratch and run that call, as ha_dedup_reduce_bags does.
+extern "C" int ha_push_apply_scaled_bags_finished(float *table, int64_t rows, int64_t width, void *plan_ws, int64_t n,
+                                                  const float *bag_grads, int64_t bag, const int32_t *bag_of, float scale,
+                                                  ha_stream_t stream) {
+    using namespace ha;
+    if (bags_args_ok("ha_push_apply_scaled_bags_finished", rows, width, n, bag, bag_of))
+        return -1;
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(table && plan_ws && bag_grads, "ha_push_apply_scaled_bags_finished: null pointer");
+    hipStream_t s = as_stream(stream);
+    const bool fixed = bag_of == nullptr;
+    if (n > kSmallMax) {
+        if (plain_launch_chunks(tolerance_tree_from(), n, width, table)) {
+            void *ws = nullptr;
+            if (scratch_get(s, static_cast<size_t>(n) * width * sizeof(float), &ws))
+                return -1;
+            hipLaunchKernelGGL(expand_bags_kernel, dim3(2048), dim3(256), 0, s, bag_grads, (int)width, n, (int)bag, bag_of,
+                               static_cast<float *>(ws));
+            HA_LAUNCH_CHECK();
+            return ha_push_apply_scaled_finished(table, rows, width, plan_ws, n, static_cast<const float *>(ws), scale, stream);
+        }
+        ApplyMaps maps{};
+        maps.valmap = bag_of;
+        maps.valdiv = fixed ? static_cast<int>(bag) : 0;
+        return apply_by_unique_impl<kModePush, true>(table, rows, width, plan_ws, n, bag_grads, scale, s, maps);
+    }
+    ha_plan_view v;
+    if (ha_plan_view_of(plan_ws, n, &v) != 0)
+        return -1;
+    const unsigned blocks = static_cast<unsigned>((n + kPosPerBlock - 1) / kPosPerBlock);
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(bag_grads) % 16 == 0);
+    static DeviceOnce lds_allowed;
+    if (lds_allowed.run([]() -> int {
+            HA_ALLOW_LDS((push_bags_kernel<4, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((push_bags_kernel<4, false>), kApplyLdsBytes);
+            HA_ALLOW_LDS((push_bags_kernel<1, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((push_bags_kernel<1, false>), kApplyLdsBytes);
+            return 0;
+        }))
+        return -1;
+#define HA_PBAGS_CASE(V, F)                                                                                              \
+    hipLaunchKernelGGL((push_bags_kernel<V, F>), dim3(blocks), dim3(1024), kApplyLdsBytes, s, table, (uint64_t)rows,     \
+                       (int)width, v.sorted, v.perm, v.upos, (int)n, bag_grads, scale, tolerance_tree_from(), (int)bag, bag_of)
+    if (vec_ok && fixed) HA_PBAGS_CASE(4, true);
+    else if (vec_ok) HA_PBAGS_CASE(4, false);
+    else if (fixed) HA_PBAGS_CASE(1, true);
+    else HA_PBAGS_CASE(1, false);
+#undef HA_PBAGS_CASE
     HA_LAUNCH_CHECK();
     return 0;
 }

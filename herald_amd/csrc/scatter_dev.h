@@ -50,8 +50,8 @@ struct ApplyMaps {
     // kPosKeep (a planned push-pull step): the pushed line is pulled in the same step, and Line::addup of that pull still sees
     // the gradient (cache.cc:404 runs in front of zeroGrad, :419) -- the first destination keeps its new value instead of zeros
     const int *victim_row;
-    // pooled gradients (sum-pooled lookup, bagsum.hip; the BAGS kernels of kModeSgd / kModeOpt / kModeReduce only, every other
-    // kernel ignores it): fixed bags of
+    // pooled gradients (sum-pooled lookup, bagsum.hip; the BAGS kernels of kModeSgd / kModePush / kModeOpt / kModeReduce only,
+    // every other kernel ignores it): fixed bags of
     // `valdiv` ids -- the source row of occurrence i is i / valdiv, computed in registers (0 = none; ragged bags give their
     // bag_of[n] as valmap instead)
     int valdiv;

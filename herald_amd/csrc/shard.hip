@@ -1433,3 +1433,142 @@ extern "C" int ha_shard_steps(float *table, int64_t rows, int64_t width, int64_t
             return -1;
     return 0;
 }
+
+// ---- the same on SUM-POOLED access (bags: ha_gather_sum_*, bagsum.hip) -----------------------------------------------------
+// The rows that cross the fabric are those of the unpooled step -- one per unique key, both ways -- so the owner gather, the two
+// exchanges and the owner merge are the calls above; only the launches at this rank's own end differ:
+//   pull half  ... -> per bag the position-ordered sum of the rows from the own shard / the received rows (ha_gather2_sum_u32map:
+//              no [n, width] rows written and read back);
+//   push half  occurrence-ordered reduce of scale * bag_grads[bag of i] by unique key into the push buffer (ha_apply_mapped_bags:
+//              no [B, width] -> [n, width] expansion) -> ...;
+//   world 1    the pooled lookup + ONE reduce-and-add launch (ha_push_apply_scaled_bags_finished).
+// Per step: nbags bags, bag >= 1 ids each (fixed: n == nbags * bag) or bag == 0 with offsets (device int64[nbags + 1], the pull)
+// and bag_of (device int32[n] from ha_bag_of, the push); out and bag_grads are [nbags, width].  Every argument of every step is
+// checked before the first launch or exchange is enqueued.
+static int shard_bags_check(const char *what, const void *table, int64_t rows, int64_t width, const ha_shard_slot *slot,
+                            const void *xchg, bool pull, const float *pull_send, const float *pull_recv, int64_t pull_rows,
+                            bool push, const float *push_buf, int64_t push_rows, const uint8_t *zero_flags, int64_t nbags, int64_t bag, const int64_t *offsets,
+                            const int32_t *bag_of, const float *out, const float *bag_grads) {
+    HA_REQUIRE(table && slot && slot->world >= 1 && slot->world <= 1024 && slot->rank >= 0 && slot->rank < slot->world &&
+                   rows >= 0 && width >= 1 && width < (1ll << 30), "%s: bad arguments", what);
+    HA_REQUIRE((!pull || pull_rows >= 0) && (!push || push_rows >= 0), "%s: bad buffer sizes pull_rows=%ld push_rows=%ld", what,
+               (long)pull_rows, (long)push_rows);
+    HA_REQUIRE(slot->n >= 0 && slot->n < (1ll << 31) && nbags >= 0 && nbags < (1ll << 31) && bag >= 0, "%s: bad sizes n=%ld nbags=%ld bag=%ld",
+               what, (long)slot->n, (long)nbags, (long)bag);
+    if (bag >= 1)
+        HA_REQUIRE(slot->n % bag == 0 && slot->n / bag == nbags, "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+                   (long)slot->n, (long)nbags, (long)bag);
+    else
+        HA_REQUIRE(slot->n == 0 || nbags >= 1, "%s: %ld ids in no bag", what, (long)slot->n);
+    if (pull) {
+        HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld)", what, (long)bag);
+        HA_REQUIRE(nbags == 0 || (out && (slot->posmap || slot->n == 0)), "%s: null output or position map", what);
+        HA_REQUIRE(slot->world == 1 || (xchg && slot->counts_host && pull_send && pull_recv && slot->keys_fixed && slot->meta_dev),
+                   "%s: world > 1 needs the exchange, the counts and the row buffers", what);
+    }
+    if (push) {
+        HA_REQUIRE(slot->n == 0 || ((bag >= 1) != (bag_of != nullptr)), "%s: give exactly one of bag >= 1 and bag_of (bag=%ld)", what,
+                   (long)bag);
+        HA_REQUIRE(slot->n == 0 || (bag_grads && slot->plan_ws), "%s: null gradient or plan", what);
+        HA_REQUIRE(slot->world == 1 || (xchg && slot->counts_host && push_buf && zero_flags && slot->owner_plan_ws &&
+                                        slot->keys_fixed && slot->meta_dev && (slot->rowmap || slot->n == 0)),
+                   "%s: world > 1 needs the exchange, the counts, the push buffer and the owner's plan workspace", what);
+    }
+    return 0;
+}
+
+static int shard_pull_sum_run(const float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg,
+                              float *pull_send, float *pull_recv, int64_t pull_rows, int64_t nbags, int64_t bag,
+                              const int64_t *offsets, float *out, ha_stream_t stream) {
+    const int w = slot->world, r = slot->rank;
+    if (w > 1) {
+        int64_t ins[1024], outs[1024];
+        for (int g = 0; g < w; ++g) {
+            ins[g] = g == r ? 0 : slot->counts_host[2 + w + g];       // rows this rank serves to peer g
+            outs[g] = g == r ? 0 : slot->counts_host[2 + g];          // rows owner g sends back
+        }
+        if (ha_shard_sized_serve_pull(table, rows, width, slot->keys_fixed, w, r, slot->rcap, slot->meta_dev, pull_send, stream))
+            return -1;
+        if (ha_xchg_rows(xchg, pull_send, ins, pull_recv, outs, width, stream))
+            return -1;
+    }
+    if (nbags > 0)
+        return ha_gather2_sum_u32map(table, rows, pull_recv, pull_recv ? pull_rows : 0, width, slot->posmap, slot->n, bag, offsets,
+                                     nbags, out, stream);
+    return 0;
+}
+
+static int shard_push_bags_run(float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg, float *push_buf,
+                               int64_t push_rows, const uint8_t *zero_flags, const float *bag_grads, int64_t bag,
+                               const int32_t *bag_of, float scale, ha_stream_t stream) {
+    const int w = slot->world, r = slot->rank;
+    if (w == 1) {      // nobody else pushes: reduce + server add of the own keys in one launch
+        if (slot->n > 0)
+            return ha_push_apply_scaled_bags_finished(table, rows, width, slot->plan_ws, slot->n, bag_grads, bag, bag_of, scale,
+                                                      stream);
+        return 0;
+    }
+    int64_t ins[1024], outs[1024], total = 0;
+    for (int g = 0; g < w; ++g) {
+        ins[g] = g == r ? 0 : slot->counts_host[2 + g];               // reduced rows for owner g
+        outs[g] = g == r ? 0 : slot->counts_host[2 + w + g];          // rows peer g pushes to this rank
+        total += slot->counts_host[2 + w + g];
+    }
+    if (slot->n > 0 && ha_apply_mapped_bags(push_buf, push_rows, width, slot->plan_ws, slot->n, bag_grads, -scale, slot->rowmap, bag,
+                                            bag_of, zero_flags, stream))
+        return -1;
+    float *recv = push_buf + static_cast<int64_t>(w + 1) * slot->rcap * width;      // region B: rows received
+    if (ha_xchg_rows(xchg, push_buf, ins, recv, outs, width, stream))
+        return -1;
+    return ha_shard_sized_serve_push(table, rows, width, slot->keys_fixed, w, r, slot->rcap, slot->meta_dev, total, push_buf,
+                                     slot->owner_plan_ws, stream);
+}
+
+extern "C" int ha_shard_step_pull_sum(const float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg,
+                                      float *pull_send, float *pull_recv, int64_t pull_rows, int64_t nbags, int64_t bag,
+                                      const int64_t *offsets, float *out, ha_stream_t stream) {
+    if (shard_bags_check("ha_shard_step_pull_sum", table, rows, width, slot, xchg, true, pull_send, pull_recv, pull_rows, false,
+                         nullptr, 0, nullptr, nbags, bag, offsets, nullptr, out, nullptr))
+        return -1;
+    return shard_pull_sum_run(table, rows, width, slot, xchg, pull_send, pull_recv, pull_rows, nbags, bag, offsets, out, stream);
+}
+
+extern "C" int ha_shard_step_push_bags(float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg,
+                                       float *push_buf, int64_t push_rows, const uint8_t *zero_flags, const float *bag_grads,
+                                       int64_t nbags, int64_t bag, const int32_t *bag_of, float scale, ha_stream_t stream) {
+    if (shard_bags_check("ha_shard_step_push_bags", table, rows, width, slot, xchg, false, nullptr, nullptr, 0, true, push_buf,
+                         push_rows, zero_flags, nbags, bag, nullptr, bag_of, nullptr, bag_grads))
+        return -1;
+    return shard_push_bags_run(table, rows, width, slot, xchg, push_buf, push_rows, zero_flags, bag_grads, bag, bag_of, scale,
+                               stream);
+}
+
+extern "C" int ha_shard_steps_bags(float *table, int64_t rows, int64_t width, int64_t count, const ha_shard_slot *const *slots,
+                                   void *xchg, float *pull_send, float *pull_recv, int64_t pull_rows, float *push_buf,
+                                   int64_t push_rows, const uint8_t *zero_flags, const int64_t *nbags, const int64_t *bag,
+                                   const int64_t *const *offsets, const int32_t *const *bag_of, float *const *outs,
+                                   const float *const *bag_grads, float scale, ha_stream_t stream) {
+    HA_REQUIRE(count >= 0 && (count == 0 || (slots && nbags && bag && offsets && bag_of && outs && bag_grads)),
+               "ha_shard_steps_bags: null pointer");
+    for (int64_t k = 0; k < count; ++k)       // every step's arguments, before the first step enqueues anything
+        if (shard_bags_check("ha_shard_steps_bags", table, rows, width, slots[k], xchg, true, pull_send, pull_recv, pull_rows, true,
+                             push_buf, push_rows, zero_flags, nbags[k], bag[k], offsets[k], bag_of[k], outs[k], bag_grads[k]))
+            return -1;
+    for (int64_t k = 0; k < count; ++k) {
+        if (shard_pull_sum_run(table, rows, width, slots[k], xchg, pull_send, pull_recv, pull_rows, nbags[k], bag[k], offsets[k],
+                               outs[k], stream))
+            return -1;
+        if (shard_push_bags_run(table, rows, width, slots[k], xchg, push_buf, push_rows, zero_flags, bag_grads[k], bag[k],
+                                bag_of[k], scale, stream))
+            return -1;
+    }
+    return 0;
+}
+
+extern "C" int ha_shard_step_bags(float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg,
+                                  float *pull_send, float *pull_recv, int64_t pull_rows, float *push_buf, int64_t push_rows,
+                                  const uint8_t *zero_flags, int64_t nbags, int64_t bag, const int64_t *offsets,
+                                  const int32_t *bag_of, float *out, const float *bag_grads, float scale, ha_stream_t stream) {
+    return ha_shard_steps_bags(table, rows, width, 1, &slot, xchg, pull_send, pull_recv, pull_rows, push_buf, push_rows, zero_flags,
+                               &nbags, &bag, &offsets, &bag_of, &out, &bag_grads, scale, stream);
+}

@@ -391,6 +391,58 @@ def gather_sum_u32keys(rows_buf, keys_i32, bag=None, offsets=None, out=None, str
     return out
 
 
+def gather2_sum_u32map(table, recv, posmap, bag=None, offsets=None, nbags=None, out=None, stream=None):
+    """The sized expand of the sharded step fused with the sum over each bag (ha_gather2_sum_u32map): position i's row is
+    table[map & 0x7FFFFFFF] if bit 31 of posmap[i] is set, else recv[map]; an index beyond its array is a zero row.  posmap
+    is an int32 tensor holding the uint32 words; table / recv may be None or have no rows.  Fixed bags: bag=F (or posmap
+    [B, F]); ragged: offsets int64 [B + 1].  Nothing but dtypes is checked here: the library checks the arguments."""
+    _require(posmap, torch.int32, "posmap")
+    n = posmap.numel()
+    src = table if table is not None else recv
+    width = src.shape[1]
+    if offsets is not None:
+        _require(offsets, torch.int64, "offsets")
+        nb = offsets.numel() - 1 if nbags is None else int(nbags)
+    else:
+        if bag is None and posmap.dim() == 2:
+            bag = posmap.shape[1]
+        nb = (n // int(bag) if bag else 0) if nbags is None else int(nbags)
+    if out is None:
+        out = torch.empty((nb, width), dtype=torch.float32, device=src.device)
+    _require(out, torch.float32, "out")
+    check(_lib.load().ha_gather2_sum_u32map(_ptr(table) if table is not None else None, table.shape[0] if table is not None else 0,
+                                            _ptr(recv) if recv is not None else None, recv.shape[0] if recv is not None else 0,
+                                            width, _ptr(posmap) if n else None, n, int(bag) if bag is not None else 0,
+                                            _ptr(offsets) if offsets is not None else None, nb, _ptr(out), _stream_ptr(stream)),
+          "ha_gather2_sum_u32map")
+    return out
+
+
+def apply_mapped_bags(dst, plan, bag_grads, lr, rowmap=None, bag=None, bag_of=None, dst_init=None, stream=None):
+    """apply_mapped's reduce on the POOLED gradient bag_grads [B, width] (ha_apply_mapped_bags): bit for bit ha_apply_mapped
+    on bag_grads expanded to [n, width].  Give `bag` (fixed) or `bag_of` (int32 [n]).  The plan must be finished."""
+    _require(dst, torch.float32, "dst")
+    _require(bag_grads, torch.float32, "bag_grads")
+    check(_lib.load().ha_apply_mapped_bags(_ptr(dst), dst.shape[0], dst.shape[1], _ptr(plan.ws), plan.n, _ptr(bag_grads),
+                                           ctypes.c_float(lr), _ptr(rowmap) if rowmap is not None else None,
+                                           int(bag) if bag is not None else 0, _ptr(bag_of) if bag_of is not None else None,
+                                           _ptr(dst_init) if dst_init is not None else None, _stream_ptr(stream)),
+          "ha_apply_mapped_bags")
+    return dst
+
+
+def push_apply_scaled_bags_finished(table, plan, bag_grads, scale, bag=None, bag_of=None, stream=None):
+    """table[key,:] += (0 + scale * g_i0) + scale * g_i1 ... with g_i = bag_grads[bag of i,:] (a finished plan): bit for bit
+    ha_push_apply_scaled_finished on bag_grads expanded to [n, width] (ha_push_apply_scaled_bags_finished)."""
+    _require(table, torch.float32, "table")
+    _require(bag_grads, torch.float32, "bag_grads")
+    check(_lib.load().ha_push_apply_scaled_bags_finished(_ptr(table), table.shape[0], table.shape[1], _ptr(plan.ws), plan.n,
+                                                         _ptr(bag_grads), int(bag) if bag is not None else 0,
+                                                         _ptr(bag_of) if bag_of is not None else None, ctypes.c_float(scale),
+                                                         _stream_ptr(stream)), "ha_push_apply_scaled_bags_finished")
+    return table
+
+
 def dedup_reduce_bags(plan, bag_grads, bag=None, bag_of=None, scale=None, out=None, stream=None):
     """dedup_reduce on the POOLED gradient bag_grads [B, width] of a sum-pooled lookup: reduced[u,:] = sum of (scale *) the
     bag rows of unique key u's occurrences in occurrence order -- bit for bit dedup_reduce on bag_grads expanded to

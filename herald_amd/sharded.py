@@ -463,6 +463,67 @@ class HipEngine:
                           i64(table.shape[0]), i64(table.shape[1]), vp(fb.plan.ws.data_ptr()), i64(fb.n),
                           vp(values.data_ptr()), ctypes.c_float(scale), vp(self._stream()))
 
+    # -- the same end launches on sum-pooled access (lay: a BagLayout -- fixed bags of lay.bag ids, or lay.bag == 0 with
+    #    lay.offsets for the pull and lay.bag_of, filled by bag_of_call, for the push) -------------------------------------------
+    def sized_expand_sum_call(self, table, rows_recv, fb, lay, out):
+        """out[b, :] = the position-ordered sum over bag b of the rows sized_expand_call would write."""
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        return self._call(self.lib.ha_gather2_sum_u32map, "ha_gather2_sum_u32map", vp(table.data_ptr()), i64(table.shape[0]),
+                          vp(rows_recv.data_ptr()), i64(rows_recv.shape[0]), i64(table.shape[1]), vp(fb.posmap.data_ptr()),
+                          i64(fb.n), i64(lay.bag), vp(lay.offsets.data_ptr() if lay.offsets is not None else None),
+                          i64(lay.nbags), vp(out.data_ptr()), vp(self._stream()))
+
+    def frames_expand_sum_call(self, rows_recv, fb, lay, out):
+        """The same over the received row FRAMES, posmap as keys (a slot beyond the frames is a zero row)."""
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        return self._call(self.lib.ha_gather_sum_u32keys, "ha_gather_sum_u32keys", vp(rows_recv.data_ptr()),
+                          i64(rows_recv.shape[0]), i64(rows_recv.shape[1]), vp(fb.posmap.data_ptr()), i64(fb.n), i64(lay.bag),
+                          vp(lay.offsets.data_ptr() if lay.offsets is not None else None), i64(lay.nbags), vp(out.data_ptr()),
+                          vp(self._stream()))
+
+    def mapped_reduce_bags_call(self, fb, bag_values, scale, dst, dst_rows, zero_flags, lay):
+        """sized_reduce_call / frames_reduce_call on the pooled values [B, width]: no expanded [n, width] values."""
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        return self._call(self.lib.ha_apply_mapped_bags, "ha_apply_mapped_bags", vp(dst.data_ptr()), i64(dst_rows),
+                          i64(dst.shape[1]), vp(fb.plan.ws.data_ptr()), i64(fb.n), vp(bag_values.data_ptr()),
+                          ctypes.c_float(-scale), vp(fb.rowmap.data_ptr()), i64(lay.bag),
+                          vp(lay.bag_of.data_ptr() if lay.bag == 0 else None), vp(zero_flags.data_ptr()), vp(self._stream()))
+
+    def sized_push_alone_bags_call(self, table, fb, bag_values, scale, lay):
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        return self._call(self.lib.ha_push_apply_scaled_bags_finished, "ha_push_apply_scaled_bags_finished",
+                          vp(table.data_ptr()), i64(table.shape[0]), i64(table.shape[1]), vp(fb.plan.ws.data_ptr()), i64(fb.n),
+                          vp(bag_values.data_ptr()), i64(lay.bag), vp(lay.bag_of.data_ptr() if lay.bag == 0 else None),
+                          ctypes.c_float(scale), vp(self._stream()))
+
+    def bag_of_call(self, lay, n):
+        """lay.bag_of[i] = the bag of position i of ragged bags (what the pooled reduces read)."""
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        return self._call(self.lib.ha_bag_of, "ha_bag_of", vp(lay.offsets.data_ptr()), i64(lay.nbags), i64(n),
+                          vp(lay.bag_of.data_ptr()), vp(self._stream()))
+
+    def sized_expand_sum(self, table, rows_recv, fb, lay, out):
+        self.sized_expand_sum_call(table, rows_recv, fb, lay, out)()
+
+    def frames_expand_sum(self, rows_recv, fb, lay, out):
+        self.frames_expand_sum_call(rows_recv, fb, lay, out)()
+
+    def bag_of(self, lay, n):
+        if lay.bag == 0 and n:
+            self.bag_of_call(lay, n)()
+
+    def sized_reduce_bags(self, fb, bag_values, scale, push_buf, zero_flags, lay):
+        if fb.n:
+            self.mapped_reduce_bags_call(fb, bag_values, scale, push_buf, push_buf.shape[0], zero_flags, lay)()
+
+    def frames_reduce_bags(self, fb, bag_values, scale, rows_send, zero_flags, lay):
+        if fb.n:
+            self.mapped_reduce_bags_call(fb, bag_values, scale, rows_send, fb.w * fb.rcap, zero_flags, lay)()
+
+    def sized_push_alone_bags(self, table, fb, bag_values, scale, lay):
+        if fb.n:
+            self.sized_push_alone_bags_call(table, fb, bag_values, scale, lay)()
+
     def sized_serve_pull(self, table, fb, rank, rows_send):
         self.sized_serve_pull_call(table, fb, rank, rows_send)()
 
@@ -548,6 +609,17 @@ class FrameBuffers:
     """Per-batch buffers inside a FrameBlock."""
     __slots__ = ("i", "w", "rcap", "stride", "plan", "keys_fixed", "rowmap", "posmap", "state_host", "state_c", "meta_dev", "out_shape",
                  "ids", "n", "shape", "routed", "send_cnt", "recv_cnt", "pos_local")
+
+
+class BagLayout:
+    """Bags of one pooled FramedStep call: fixed bags of `bag` ids, or bag == 0 with int64 offsets[nbags + 1] on the device
+    (and, for a push, bag_of = the ring slot's int32 buffer the bag of every position is written to).  key: what the layout
+    adds to the keys of cached calls and graphs."""
+    __slots__ = ("bag", "nbags", "offsets", "bag_of", "key")
+
+    def __init__(self, bag, nbags, offsets, bag_of=None):
+        self.bag, self.nbags, self.offsets, self.bag_of = int(bag or 0), int(nbags), offsets, bag_of
+        self.key = ("bags", self.bag, self.nbags, offsets.data_ptr() if offsets is not None else 0)
 
 
 class RouteBuffers:
@@ -875,7 +947,10 @@ class ShardedEmbedding:
         int64 offsets[B + 1] on the store's device.  Raises ValueError -- before the caller enters any collective."""
         if ids is None and route is None:
             raise ValueError("%s: give ids or a route" % what)
-        shape = tuple(ids.shape) if ids is not None else route.shape
+        return self._bag_layout_of(what, tuple(ids.shape) if ids is not None else route.shape, offsets)
+
+    def _bag_layout_of(self, what, shape, offsets):
+        """_bag_layout of a batch whose ids have `shape` (FramedStep: the shape a batch was staged with)."""
         if offsets is None:
             if len(shape) != 2 or shape[1] < 1:
                 raise ValueError("%s: fixed bags need ids of shape [B, F], got %s; give offsets for ragged bags"
@@ -1052,6 +1127,7 @@ class FramedStep:
         self._ring = 3 * self.block
         self._slot_of = [(self.blocks[(j // self.block) % 3], self.blocks[(j // self.block) % 3].slots[j % self.block])
                          for j in range(3 * self.block)]
+        self._bag_of = {}            # ring slot -> bag_of[max_ids] of a batch of ragged bags pushed from it (push_bags)
         emb._frame(self.max_ids)     # the sized path (overflowed batches) agrees on its frame now, on every rank
 
     # -- plumbing ---------------------------------------------------------------------------------------------------
@@ -1127,15 +1203,22 @@ class FramedStep:
         self.eng.wait_event(self.blocks[b % 3].ev)
         self._route_block(b + 1)
 
-    def _pull(self, j, out):
+    def _pull(self, j, out, lay=None):
         blk, fb = self._fb(j)
         self.eng.frames_serve_pull(self.emb.table, blk, fb, self.pull_send)
         got = self._exchange(self.pull_recv, self.pull_send)
-        self.eng.frames_expand(got, fb, out)
+        if lay is None:
+            self.eng.frames_expand(got, fb, out)
+        elif lay.nbags:
+            self.eng.frames_expand_sum(got, fb, lay, out)
 
-    def _push(self, j, values, scale):
+    def _push(self, j, values, scale, lay=None):
         _, fb = self._fb(j)
-        self.eng.frames_reduce(fb, values, scale, self.push_send, self.zero_flags)
+        if lay is None:
+            self.eng.frames_reduce(fb, values, scale, self.push_send, self.zero_flags)
+        else:
+            self.eng.bag_of(lay, fb.n)
+            self.eng.frames_reduce_bags(fb, values, scale, self.push_send, self.zero_flags, lay)
         got = self._exchange(self.push_recv, self.push_send)
         self.eng.frames_serve_push(self.emb.table, fb, got)
 
@@ -1145,16 +1228,21 @@ class FramedStep:
             fb.send_cnt, fb.recv_cnt = self.eng.frames_counts(fb)
         return fb.send_cnt, fb.recv_cnt
 
-    def _pull_sized(self, j, out, stream_key):
+    def _pull_sized(self, j, out, stream_key, lay=None):
         blk, fb = self._slot_of[j % self._ring]
         eng, emb = self.eng, self.emb
         w, r = emb.world, emb.rank
+        if lay is not None:
+            expand = lambda: eng.sized_expand_sum_call(emb.table, self.pull_recv, fb, lay, out)
+            live, ekey = lay.nbags, ("sexp", j % self._ring, fb.n, out.data_ptr() if lay.nbags else 0, stream_key) + lay.key
+        else:
+            expand = lambda: eng.sized_expand_call(emb.table, self.pull_recv, fb, out)
+            live, ekey = fb.n, ("sexp", j % self._ring, fb.n, out.data_ptr() if fb.n else 0, stream_key)
         if w == 1 and self._fast_ok:       # the whole pull is one launch; its arguments are converted once per buffer set
-            if fb.n:
-                key = ("sexp", j % self._ring, fb.n, out.data_ptr(), stream_key)
-                c = self._calls.get(key)
+            if live:
+                c = self._calls.get(ekey)
                 if c is None:
-                    c = self._fast(key, lambda: eng.sized_expand_call(emb.table, self.pull_recv, fb, out))
+                    c = self._fast(ekey, expand)
                 c()
             return
         if w > 1:
@@ -1168,33 +1256,47 @@ class FramedStep:
                 eng.sized_serve_pull(emb.table, fb, r, self.pull_send)
             emb._a2a(self.pull_recv[:sum(outs)], self.pull_send[:sum(ins)], outs, ins)
             self._account_sized(ins, outs, send_cnt, recv_cnt)
-        if fb.n:
+        if live:
             if self._fast_ok:
-                self._fast(("sexp", j % self._ring, fb.n, out.data_ptr(), stream_key),
-                           lambda: eng.sized_expand_call(emb.table, self.pull_recv, fb, out))()
+                self._fast(ekey, expand)()
+            elif lay is not None:
+                eng.sized_expand_sum(emb.table, self.pull_recv, fb, lay, out)
             else:
                 eng.sized_expand(emb.table, self.pull_recv, fb, out)
 
-    def _push_sized(self, j, values, scale, stream_key):
+    def _push_sized(self, j, values, scale, stream_key, lay=None):
         _, fb = self._slot_of[j % self._ring]
         eng, emb = self.eng, self.emb
         w, r = emb.world, emb.rank
+        lk = () if lay is None else lay.key
+        if lay is not None and lay.bag == 0 and fb.n:      # ragged bags: the bag of every position, into the slot's buffer
+            if self._fast_ok:
+                self._fast(("bagof", j % self._ring, fb.n, stream_key) + lk, lambda: eng.bag_of_call(lay, fb.n))()
+            else:
+                eng.bag_of(lay, fb.n)
         if w == 1:          # nobody else pushes: reduce + server add of the own keys in one launch
             if fb.n:
                 if self._fast_ok:
-                    key = ("salone", j % self._ring, fb.n, values.data_ptr(), scale, stream_key)
+                    key = ("salone", j % self._ring, fb.n, values.data_ptr(), scale, stream_key) + lk
                     c = self._calls.get(key)
                     if c is None:
-                        c = self._fast(key, lambda: eng.sized_push_alone_call(emb.table, fb, values, scale))
+                        c = self._fast(key, (lambda: eng.sized_push_alone_call(emb.table, fb, values, scale)) if lay is None else
+                                       (lambda: eng.sized_push_alone_bags_call(emb.table, fb, values, scale, lay)))
                     c()
+                elif lay is not None:
+                    eng.sized_push_alone_bags(emb.table, fb, values, scale, lay)
                 else:
                     eng.sized_push_alone(emb.table, fb, values, scale)
             return
         send_cnt, recv_cnt = self._counts(fb)
         if fb.n:
             if self._fast_ok:
-                self._fast(("sred", j % self._ring, fb.n, values.data_ptr(), scale, stream_key),
-                           lambda: eng.sized_reduce_call(fb, values, scale, self.push_buf, self.zero_flags))()
+                self._fast(("sred", j % self._ring, fb.n, values.data_ptr(), scale, stream_key) + lk,
+                           (lambda: eng.sized_reduce_call(fb, values, scale, self.push_buf, self.zero_flags)) if lay is None else
+                           (lambda: eng.mapped_reduce_bags_call(fb, values, scale, self.push_buf, self.push_buf.shape[0],
+                                                                self.zero_flags, lay)))()
+            elif lay is not None:
+                eng.sized_reduce_bags(fb, values, scale, self.push_buf, self.zero_flags, lay)
             else:
                 eng.sized_reduce(fb, values, scale, self.push_buf, self.zero_flags)
         ins = [c if g != r else 0 for g, c in enumerate(send_cnt)]          # reduced rows for owner g
@@ -1230,25 +1332,39 @@ class FramedStep:
             c = self._calls[key] = build()
         return c
 
-    def _pull_fast(self, j, out, stream_key):
+    def _pull_fast(self, j, out, stream_key, lay=None):
         blk, fb = self._fb(j)
         eng, emb = self.eng, self.emb
         rows_in = self.pull_send if emb.world == 1 else self.pull_recv
-        a, b = self._fast(("pull", j % self._ring, fb.n, out.data_ptr() if fb.n else 0, blk.kgot.data_ptr(), stream_key),
-                          lambda: (eng.frames_serve_pull_call(emb.table, blk, fb, self.pull_send),
-                                   eng.frames_expand_call(rows_in, fb, out) if fb.n else None))
+        if lay is None:
+            a, b = self._fast(("pull", j % self._ring, fb.n, out.data_ptr() if fb.n else 0, blk.kgot.data_ptr(), stream_key),
+                              lambda: (eng.frames_serve_pull_call(emb.table, blk, fb, self.pull_send),
+                                       eng.frames_expand_call(rows_in, fb, out) if fb.n else None))
+        else:
+            a, b = self._fast(("pull", j % self._ring, fb.n, out.data_ptr() if lay.nbags else 0, blk.kgot.data_ptr(),
+                               stream_key) + lay.key,
+                              lambda: (eng.frames_serve_pull_call(emb.table, blk, fb, self.pull_send),
+                                       eng.frames_expand_sum_call(rows_in, fb, lay, out) if lay.nbags else None))
         a()
         self._exchange(self.pull_recv, self.pull_send)
         if b is not None:
             b()
 
-    def _push_fast(self, j, values, scale, stream_key):
+    def _push_fast(self, j, values, scale, stream_key, lay=None):
         _, fb = self._fb(j)
         eng, emb = self.eng, self.emb
         rows_in = self.push_send if emb.world == 1 else self.push_recv
-        a, b = self._fast(("push", j % self._ring, fb.n, values.data_ptr() if fb.n else 0, scale, stream_key),
-                          lambda: (eng.frames_reduce_call(fb, values, scale, self.push_send, self.zero_flags) if fb.n else None,
-                                   eng.frames_serve_push_call(emb.table, fb, rows_in)))
+        if lay is None:
+            a, b = self._fast(("push", j % self._ring, fb.n, values.data_ptr() if fb.n else 0, scale, stream_key),
+                              lambda: (eng.frames_reduce_call(fb, values, scale, self.push_send, self.zero_flags) if fb.n else None,
+                                       eng.frames_serve_push_call(emb.table, fb, rows_in)))
+        else:
+            if lay.bag == 0 and fb.n:
+                self._fast(("bagof", j % self._ring, fb.n, stream_key) + lay.key, lambda: eng.bag_of_call(lay, fb.n))()
+            a, b = self._fast(("push", j % self._ring, fb.n, values.data_ptr() if fb.n else 0, scale, stream_key) + lay.key,
+                              lambda: (eng.mapped_reduce_bags_call(fb, values, scale, self.push_send, fb.w * fb.rcap,
+                                                                   self.zero_flags, lay) if fb.n else None,
+                                       eng.frames_serve_push_call(emb.table, fb, rows_in)))
         if a is not None:
             a()
         self._exchange(self.push_recv, self.push_send)
@@ -1311,14 +1427,24 @@ class FramedStep:
 
     def pull(self, ahead_ids=None, out=None, _block_started=False):
         """Rows of the current batch k; `ahead_ids` = batch k + LOOKAHEAD (None once the stream has ended)."""
+        self._current_for_pull("pull")
+        return self._pull_step(ahead_ids, out, _block_started, None)
+
+    def _current_for_pull(self, what):
+        """The routed batch the next pull serves; the protocol errors of pull / pull_sum."""
         if self.k is None:
-            raise RuntimeError("FramedStep.pull before start")
+            raise RuntimeError("FramedStep.%s before start" % what)
         if self._pending:
             raise RuntimeError("FramedStep: pull and push alternate (push the current batch first)")
+        fb = self._slot_of[self.k % self._ring][1]
+        if not fb.routed:
+            raise RuntimeError("FramedStep.%s: the stream of batches has ended" % what)
+        return fb
+
+    def _pull_step(self, ahead_ids, out, _block_started, lay):
+        """pull (lay None) / pull_sum (lay: the batch's BagLayout) of the current batch; arguments are checked by now."""
         k = self.k
         blk, fb = self._slot_of[k % self._ring]
-        if not fb.routed:
-            raise RuntimeError("FramedStep.pull: the stream of batches has ended")
         if k % self.block == 0 and not _block_started:
             self._block_start(k // self.block)
         self._stage(k + self.LOOKAHEAD, ahead_ids)
@@ -1327,51 +1453,103 @@ class FramedStep:
             blk.synced = True
         self._over = over = self.eng.frames_overflowed(fb)
         width = self.emb.width
-        if fb.n and out is None:
-            out = self.eng.empty_rows(fb.n, width)
+        live = fb.n if lay is None else lay.nbags          # rows of the result
+        if live and out is None:
+            out = self.eng.empty_rows(live, width)
         if over:
             # sized exchange for this batch only (a collective: every rank saw the flag)
             self.fallbacks += 1
             self._sized = self.emb.prefetch(fb.ids)
-            rows = self.emb.pull(route=self._sized, return_route=False)
-            if fb.n:
+            if lay is None:
+                rows = self.emb.pull(route=self._sized, return_route=False)
+            else:
+                rows = self.emb.pull_sum(fb.ids.reshape(fb.shape), offsets=lay.offsets, route=self._sized)
+            if live:
                 out.copy_(rows.reshape(out.shape))
         elif self.sized:
-            self._pull_sized(k, out, self.eng._stream() if self._fast_ok else 0)
+            self._pull_sized(k, out, self.eng._stream() if self._fast_ok else 0, lay)
         else:
             if self._fast_ok and not self.graphs:
-                self._pull_fast(k, out, self.eng._stream())
+                self._pull_fast(k, out, self.eng._stream(), lay)
             else:
-                self._run(("pull", k % self._ring, fb.n, out.data_ptr() if fb.n else 0), lambda: self._pull(k, out))
+                self._run(("pull", k % self._ring, fb.n, out.data_ptr() if live else 0) + (() if lay is None else lay.key),
+                          lambda: self._pull(k, out, lay))
             self._account()
         self._pending = True
-        if not fb.n:
+        if not live:
             return None
+        if lay is not None:
+            return out
         return out if out.shape == fb.out_shape else out.reshape(fb.out_shape)
 
     def push(self, values, lr=None):
         """Apply the gradients `values` of the current batch on its owners (scale -lr; 1 if lr is None)."""
         if not self._pending:
             raise RuntimeError("FramedStep: pull and push alternate (pull the current batch first)")
+        self._push_step(values, lr, None)
+
+    def _push_step(self, values, lr, lay):
+        """push (lay None) / push_bags (lay: the batch's BagLayout, values = [B, width]); arguments are checked by now."""
         k = self.k
         _, fb = self._slot_of[k % self._ring]
         scale = 1.0 if lr is None else -float(lr)
         if self._over:
-            self.emb.push(None, values, lr, route=self._sized)
+            if lay is None:
+                self.emb.push(None, values, lr, route=self._sized)
+            else:
+                self.emb.push_bags(fb.ids.reshape(fb.shape), values, lr, offsets=lay.offsets, route=self._sized)
             self._sized = None
         else:
             v = None
-            if fb.n:        # the launches read `values` as [n, width] rows
+            if fb.n:        # the launches read `values` as [n, width] rows ([B, width] rows of the bags: pooled)
                 v = values if values.dim() == 2 and values.is_contiguous() else values.reshape(-1, self.emb.width).contiguous()
             if self.sized:
-                self._push_sized(k, v, scale, self.eng._stream() if self._fast_ok else 0)
+                self._push_sized(k, v, scale, self.eng._stream() if self._fast_ok else 0, lay)
             elif self._fast_ok and not self.graphs:
-                self._push_fast(k, v, scale, self.eng._stream())
+                self._push_fast(k, v, scale, self.eng._stream(), lay)
             else:
-                self._run(("push", k % self._ring, fb.n, v.data_ptr() if fb.n else 0, scale),
-                          lambda: self._push(k, v, scale))
+                self._run(("push", k % self._ring, fb.n, v.data_ptr() if fb.n else 0, scale) + (() if lay is None else lay.key),
+                          lambda: self._push(k, v, scale, lay))
         self._pending = False
         self.k = k + 1
+
+    # -- sum-pooled access (embedding_lookup_op + reduce_sum_op(axes=1) of the reference's emb_sum_* models) -----------------
+    # Routing, owner gather, exchanges, owner merge and `stats` are those of pull / push -- the same rows cross the fabric --;
+    # only this rank's end launches differ (csrc/shard.hip): the pull sums each bag straight out of the own shard / the received
+    # rows, the push reduces the pooled gradient [B, width] by unique key as it is.  Pooled and unpooled calls may alternate
+    # freely: a pull_sum may be followed by the push of the same batch and the reverse.
+    def _bag_layout(self, what, j, offsets, push=False):
+        """BagLayout of batch j: fixed bags from the [B, F] shape it was staged with, ragged ones from its 1-D ids and int64
+        offsets[B + 1] on the device (ShardedEmbedding._bag_layout's rules).  Raises ValueError; moves nothing."""
+        slot = j % self._ring
+        bag, nbags = self.emb._bag_layout_of(what, self._slot_of[slot][1].shape, offsets)
+        lay = BagLayout(bag, nbags, offsets)
+        if push and lay.bag == 0:
+            buf = self._bag_of.get(slot)
+            if buf is None:        # one buffer per ring slot, never moved: a cached call or a graph replay reads valid memory
+                buf = self._bag_of[slot] = self.eng.zeros((max(self.max_ids, 1),), torch.int32)
+            lay.bag_of = buf
+        return lay
+
+    def pull_sum(self, ahead_ids=None, offsets=None, out=None, _block_started=False):
+        """out[b,:] = ((0 + row of id_0) + row of id_1) + ... over bag b of the current batch in position order: pull followed
+        by the sum over each bag, bit for bit, without the [n, width] rows.  Fixed bags: the batch was staged as [B, F];
+        ragged: it was staged as [n] and `offsets` is int64 [B + 1] on the device.  Returns [B, width] (None: no bags)."""
+        self._current_for_pull("pull_sum")
+        lay = self._bag_layout("pull_sum", self.k, offsets)
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (lay.nbags, self.emb.width) or
+                                out.dtype != torch.float32 or not out.is_contiguous()):
+            raise ValueError("pull_sum: out must be contiguous float32 [%d, %d]" % (lay.nbags, self.emb.width))
+        return self._pull_step(ahead_ids, out, _block_started, lay)
+
+    def push_bags(self, bag_values, lr=None, offsets=None):
+        """push of the pooled gradient bag_values [B, width] of the current batch: every id of bag b pushes
+        -lr * bag_values[b,:] -- push of bag_values expanded to [n, width], bit for bit, without the expanded values."""
+        if not self._pending:
+            raise RuntimeError("FramedStep: pull and push alternate (pull the current batch first)")
+        lay = self._bag_layout("push_bags", self.k, offsets, push=True)
+        self.emb._check_bag_values("push_bags", bag_values, lay.nbags)
+        self._push_step(bag_values, lr, lay)
 
     # -- the step as ONE native call (ha_shard_step / ha_shard_steps, csrc/shard.hip) ---------------------------------------
     def native_ok(self):
@@ -1414,6 +1592,35 @@ class FramedStep:
         rows (a benchmark loop, a pipeline with staleness); the steps must lie in ONE routing block.  ahead_ids_list[i] = batch
         k + i + LOOKAHEAD (None entries once the stream has ended).  Falls back to pull / push step by step where the native
         step is not available or a batch of the run overflowed its key frames.  Returns the rows of the batches."""
+        return self._steps(ahead_ids_list, values_list, lr, outs, None)
+
+    def steps_bags(self, ahead_ids_list, bag_values_list, lr=None, outs=None, offsets_list=None):
+        """steps on sum-pooled access: step i is pull_sum of the current batch into outs[i] ([B, width]) and push_bags of its
+        pooled gradient bag_values_list[i] ([B, width]), the whole run by ONE library call (ha_shard_steps_bags) under the
+        rules of steps -- one routing block, the same fallbacks.  offsets_list[i]: int64 [B + 1] on the device for a batch of
+        ragged bags (staged as [n]), None for one staged as [B, F].  Returns the pooled rows of the batches."""
+        cnt = len(bag_values_list)
+        offsets_list = list(offsets_list) if offsets_list is not None else [None] * cnt
+        if len(offsets_list) != cnt or (outs is not None and len(outs) != cnt):
+            raise ValueError("steps_bags: one entry of offsets_list and of outs per step")
+        lays = []
+        if self.k is not None and not self._pending:       # (otherwise _steps raises the protocol error)
+            for i in range(cnt):
+                fb = self._slot_of[(self.k + i) % self._ring][1]
+                if not fb.routed:
+                    lays.append(None)       # (the stream has ended: the step-by-step path reports it)
+                    continue
+                lay = self._bag_layout("steps_bags", self.k + i, offsets_list[i], push=True)
+                self.emb._check_bag_values("steps_bags", bag_values_list[i], lay.nbags)
+                o = outs[i] if outs is not None else None
+                if o is not None and (not isinstance(o, torch.Tensor) or tuple(o.shape) != (lay.nbags, self.emb.width) or
+                                      o.dtype != torch.float32 or not o.is_contiguous()):
+                    raise ValueError("steps_bags: outs[%d] must be contiguous float32 [%d, %d]" % (i, lay.nbags, self.emb.width))
+                lays.append(lay)
+        return self._steps(ahead_ids_list, bag_values_list, lr, outs, (lays, offsets_list))
+
+    def _steps(self, ahead_ids_list, values_list, lr, outs, pooled):
+        """steps (pooled None) / steps_bags (pooled = (the steps' BagLayouts, their offsets))."""
         import ctypes
         if self.k is None:
             raise RuntimeError("FramedStep.steps before start")
@@ -1427,8 +1634,11 @@ class FramedStep:
             raise ValueError("steps %d..%d cross a routing block boundary (block = %d)" % (k0, k0 + cnt - 1, self.block))
         eng, emb, width = self.eng, self.emb, self.emb.width
         fbs = [self._slot_of[(k0 + i) % self._ring][1] for i in range(cnt)]
+        lays = pooled[0] if pooled is not None else None
+        # rows of step i's result: its positions, or its bags
+        live = [fb.n for fb in fbs] if lays is None else [lay.nbags if lay is not None else 0 for lay in lays]
         if outs is None:
-            outs = [eng.empty_rows(fb.n, width) if fb.n else None for fb in fbs]
+            outs = [eng.empty_rows(m, width) if m else None for m in live]
         native = native_tried = self.native_ok() and all(fb.routed for fb in fbs)
         # The host's work at a block boundary used to sit between two blocks' steps with the device idle: the routing of block
         # b + 1 was enqueued (and, the device having nothing else, executed) BEFORE the steps of block b -- 95 us of a 290 us block
@@ -1457,8 +1667,13 @@ class FramedStep:
         if not native:
             res = []
             for i in range(cnt):
-                res.append(self.pull(ahead_ids_list[i], out=outs[i], _block_started=started and i == 0))
-                self.push(values_list[i], lr)
+                if lays is None:
+                    res.append(self.pull(ahead_ids_list[i], out=outs[i], _block_started=started and i == 0))
+                    self.push(values_list[i], lr)
+                else:
+                    res.append(self.pull_sum(ahead_ids_list[i], offsets=pooled[1][i], out=outs[i],
+                                             _block_started=started and i == 0))
+                    self.push_bags(values_list[i], lr, offsets=pooled[1][i])
             return res
         for i in range(cnt):
             self._stage(k0 + i + self.LOOKAHEAD, ahead_ids_list[i])
@@ -1472,15 +1687,29 @@ class FramedStep:
                 v = v if v.dim() == 2 and v.is_contiguous() else v.reshape(-1, width).contiguous()
             vals.append(v)
         sl = (ctypes.POINTER(type(descs[0])) * cnt)(*[ctypes.pointer(d) for d in descs])
-        op = (vp * cnt)(*[o.data_ptr() if (o is not None and fb.n) else None for o, fb in zip(outs, fbs)])
+        op = (vp * cnt)(*[o.data_ptr() if (o is not None and m) else None for o, m in zip(outs, live)])
         gp = (vp * cnt)(*[v.data_ptr() if fb.n else None for v, fb in zip(vals, fbs)])
         xh = vp(emb.native.h) if emb.world > 1 else None
-        rc = eng.lib.ha_shard_steps(vp(emb.table.data_ptr()), emb.table.shape[0], width, cnt, sl, xh,
-                                    vp(self.pull_send.data_ptr()), vp(self.pull_recv.data_ptr()), self.pull_recv.shape[0],
-                                    vp(self.push_buf.data_ptr()), self.push_buf.shape[0], vp(self.zero_flags.data_ptr()), op, gp,
-                                    ctypes.c_float(scale), vp(eng._stream()))
-        if rc != 0:
-            eng.check(-1, "ha_shard_steps")
+        if lays is None:
+            rc = eng.lib.ha_shard_steps(vp(emb.table.data_ptr()), emb.table.shape[0], width, cnt, sl, xh,
+                                        vp(self.pull_send.data_ptr()), vp(self.pull_recv.data_ptr()), self.pull_recv.shape[0],
+                                        vp(self.push_buf.data_ptr()), self.push_buf.shape[0], vp(self.zero_flags.data_ptr()), op, gp,
+                                        ctypes.c_float(scale), vp(eng._stream()))
+            if rc != 0:
+                eng.check(-1, "ha_shard_steps")
+        else:
+            for lay, fb in zip(lays, fbs):       # ragged bags: the bag of every position, into the slots' own buffers
+                eng.bag_of(lay, fb.n)
+            i64s = ctypes.c_int64 * cnt
+            rc = eng.lib.ha_shard_steps_bags(
+                vp(emb.table.data_ptr()), emb.table.shape[0], width, cnt, sl, xh, vp(self.pull_send.data_ptr()),
+                vp(self.pull_recv.data_ptr()), self.pull_recv.shape[0], vp(self.push_buf.data_ptr()), self.push_buf.shape[0],
+                vp(self.zero_flags.data_ptr()), i64s(*[lay.nbags for lay in lays]), i64s(*[lay.bag for lay in lays]),
+                (vp * cnt)(*[lay.offsets.data_ptr() if lay.offsets is not None else None for lay in lays]),
+                (vp * cnt)(*[lay.bag_of.data_ptr() if (lay.bag == 0 and fb.n) else None for lay, fb in zip(lays, fbs)]),
+                op, gp, ctypes.c_float(scale), vp(eng._stream()))
+            if rc != 0:
+                eng.check(-1, "ha_shard_steps_bags")
         if route_after is not None:
             self._route_block(route_after[0], after=route_after[1])
         if (k0 + cnt) % self.block == 0:           # the block's last step is enqueued: what its successor's successor's routing waits for
@@ -1496,6 +1725,8 @@ class FramedStep:
                                     [c if g != r else 0 for g, c in enumerate(recv_cnt)], send_cnt, recv_cnt, pull=False)
         self.k = k0 + cnt
         self._keep = (vals, outs)        # (the launches read them: alive until the next call)
+        if lays is not None:
+            return [o if m else None for o, m in zip(outs, live)]
         return [None if not fb.n else (o if o.shape == fb.out_shape else o.reshape(fb.out_shape)) for o, fb in zip(outs, fbs)]
 
     # -- measurement aid (bench.py's N>1 leg): the five launches of a step one by one -----------------------------------

@@ -884,6 +884,47 @@ int ha_shard_steps(float *table, int64_t rows, int64_t width, int64_t count, con
                    float *pull_send, float *pull_recv, int64_t pull_rows, float *push_buf, int64_t push_rows,
                    const uint8_t *zero_flags, float *const *outs, const float *const *values, float scale, ha_stream_t stream);
 
+/* The same steps on SUM-POOLED access (bags, see ha_gather_sum_* below): the same owner gather, exchanges and owner merge --
+ * the rows that cross the fabric are one per unique key either way --; only this rank's own end launches differ.
+ *   ha_gather2_sum_u32map  ha_gather2_u32map fused with the sum over each bag: out[b,:] = ((0.0f + r_0) + r_1) + ... over bag
+ *     b's positions in position order, one rounding per term, r_j exactly the row ha_gather2_u32map writes for the position
+ *     (table[map & 0x7FFFFFFF] if bit 31 is set, else recv[map]; zeros for an index beyond its array, 0xFFFFFFFF included).
+ *     Bags, offset clamping, slice rule and argument rules as ha_gather_sum_*; a side without rows is never dereferenced.
+ *   ha_apply_mapped_bags   ha_apply_mapped (below) on bag_grads [nbags, width] expanded to [n, width], without the expanded
+ *     tensor: fixed bags (bag >= 1, bag_of NULL, n % bag == 0; the source row i / bag is computed in registers) or ragged ones
+ *     (bag == 0, bag_of = int32[n] from ha_bag_of).  By unique key where ha_apply_mapped goes by unique key.  Same bits.
+ *   ha_push_apply_scaled_bags_finished  ha_push_apply_scaled_finished on the expanded gradient, without it (a FINISHED plan):
+ *     the same bits in tolerance modes 0 and 1; in mode 2, where the expanded call would cut long runs into chunks, the
+ *     gradient is expanded into the library's per-stream scratch and that call runs (see ha_dedup_reduce_bags).
+ *   ha_shard_step_pull_sum / _push_bags / ha_shard_step_bags / ha_shard_steps_bags: the pooled twins of the native steps.  Per
+ *     step: nbags bags of bag ids (fixed), or bag == 0 with offsets (device int64[nbags + 1], for the pull) and bag_of (device
+ *     int32[n], for the push); out and bag_grads are [nbags, width].
+ * Every argument (of every step) is checked before any device access and before anything is enqueued. */
+int ha_gather2_sum_u32map(const float *table, int64_t rows, const float *recv, int64_t recv_rows, int64_t width,
+                          const uint32_t *map, int64_t n, int64_t bag, const int64_t *offsets, int64_t nbags, float *out,
+                          ha_stream_t stream);
+int ha_apply_mapped_bags(float *dst, int64_t dst_rows, int64_t width, const void *plan_ws, int64_t n, const float *bag_grads,
+                         float lr, const int32_t *rowmap, int64_t bag, const int32_t *bag_of, const uint8_t *dst_init,
+                         ha_stream_t stream);
+int ha_push_apply_scaled_bags_finished(float *table, int64_t rows, int64_t width, void *plan_ws, int64_t n,
+                                       const float *bag_grads, int64_t bag, const int32_t *bag_of, float scale,
+                                       ha_stream_t stream);
+int ha_shard_step_pull_sum(const float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg,
+                           float *pull_send, float *pull_recv, int64_t pull_rows, int64_t nbags, int64_t bag,
+                           const int64_t *offsets, float *out, ha_stream_t stream);
+int ha_shard_step_push_bags(float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg, float *push_buf,
+                            int64_t push_rows, const uint8_t *zero_flags, const float *bag_grads, int64_t nbags, int64_t bag,
+                            const int32_t *bag_of, float scale, ha_stream_t stream);
+int ha_shard_step_bags(float *table, int64_t rows, int64_t width, const ha_shard_slot *slot, void *xchg, float *pull_send,
+                       float *pull_recv, int64_t pull_rows, float *push_buf, int64_t push_rows, const uint8_t *zero_flags,
+                       int64_t nbags, int64_t bag, const int64_t *offsets, const int32_t *bag_of, float *out,
+                       const float *bag_grads, float scale, ha_stream_t stream);
+int ha_shard_steps_bags(float *table, int64_t rows, int64_t width, int64_t count, const ha_shard_slot *const *slots, void *xchg,
+                        float *pull_send, float *pull_recv, int64_t pull_rows, float *push_buf, int64_t push_rows,
+                        const uint8_t *zero_flags, const int64_t *nbags, const int64_t *bag, const int64_t *const *offsets,
+                        const int32_t *const *bag_of, float *const *outs, const float *const *bag_grads, float scale,
+                        ha_stream_t stream);
+
 /* Owner side of a sparse push (PSHandler::serve(SparsePush), ps-lite/include/ps/server/PSFHandle.h:130-164):
  * table[keys[j],:] = (table[keys[j],:] + values[a,:]) + values[b,:] ... over the positions a < b < ... that
  * list the key, i.e. in list order (the W received sorted lists concatenated in rank order).
