@@ -250,7 +250,7 @@ def make_batches(nbatch, batch, rows, seed=0, rank=0, world=1):
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
-          opt_fuse_bags=True, ps_fuse_bags=True):
+          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -260,6 +260,9 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     POOLED rows: the communicate op is told the bag size, the cache sums a sample's 26 rows as it reads them and takes the
     [batch, width] gradient as it is (cache_fuse_bags=False: the unfused path, the same bits).  On --embedding ps a pooled model does the same through the
     sharded store's pull_sum / push_bags on every schedule (ps_fuse_bags=False, --no-ps-fuse-bags: the unfused path, the same bits).
+    cache_fuse_bag_calls (--cache-fuse-bag-calls): a pooled model whose cache flow is call by call (no cache_planned, LFU / LFUOpt
+    at bsp < 0, world size > 1) pulls and pushes pooled rows through the cache's pooled calls as well (off: the unfused path, the
+    same bits).
     The ring wraps round, so the chain is still open when training ends, with one step's bookkeeping planned ahead and never
     run -- harmless: the store's table is written by row launches only.  LFU / LFUOpt at bsp < 0 stay call by call.  a2a / allreduce: optional
     replacements of the collectives at world size > 1 (several ranks on one GPU under gloo in the tests).
@@ -309,7 +312,7 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                  cache_limit=cache_limit if cache_limit is not None else
                                  max(rows // 10, batch * NFIELD * (2 if cache_planned and bsp < 0 else 1)),
                                  cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned, cache_fuse_bags=cache_fuse_bags,
-                                 ps_fuse_bags=ps_fuse_bags)
+                                 ps_fuse_bags=ps_fuse_bags, cache_fuse_bag_calls=cache_fuse_bag_calls)
         comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: ids_of(state["k"] + 1),
                                                      peek_ids=lambda j: ids_of(state["k"] + 1 + j),
                                                      bag=NFIELD if pooled and embedding in ("cache", "ps") else None)
@@ -479,6 +482,10 @@ def main():
     ap.add_argument("--no-ps-fuse-bags", action="store_true",
                     help="--embedding ps with --model emb_sum_wdl: pull per-occurrence rows and push the expanded gradient "
                          "instead of the store's pooled pull_sum / push_bags (the same bits)")
+    ap.add_argument("--cache-fuse-bag-calls", action="store_true",
+                    help="--embedding cache with --model emb_sum_wdl where the cache is used call by call (no --cache-planned, "
+                         "lfu / lfuopt at --bsp -1, world size > 1): pull pooled rows (embedding_lookup_sum) and push the "
+                         "[batch, width] gradient as it is (embedding_update_bags / embedding_push_pull_bags) -- the same bits")
     ap.add_argument("--nepoch", type=int, default=-1, help="epochs of `--steps` steps each (default: one)")
     ap.add_argument("--embedding", choices=["hbm", "step", "step3", "queue", "ps", "cache"], default=None,
                     help="this build's engine names; default: from --comm / --cache")
@@ -525,7 +532,7 @@ def main():
                        args.bound, cache_limit=cache_limit, device="cuda:%d" % local_rank,
                        log_every=max(1, args.steps // 10), model=args.model, bsp=args.bsp if comm is not None else 0,
                        cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer,
-                       ps_fuse_bags=not args.no_ps_fuse_bags)[0]
+                       ps_fuse_bags=not args.no_ps_fuse_bags, cache_fuse_bag_calls=args.cache_fuse_bag_calls)[0]
     if local_rank == 0:
         print("first 10 steps: loss %.5f   last 10 steps: loss %.5f" % (np.mean(losses[:10]), np.mean(losses[-10:])))
 

@@ -156,6 +156,7 @@ def _declare(L):
         "ha_dedup_reduce": [vp, i64, vp, i64, vp, vp],
         "ha_apply_mapped": [vp, i64, i64, vp, i64, vp, f32, vp, vp, vp, vp],
         "ha_apply_mapped2": [vp, i64, vp, i64, vp, i64, vp, f32, vp, vp, vp, vp],
+        "ha_apply_mapped2_bags": [vp, i64, vp, i64, vp, i64, vp, f32, vp, vp, i64, vp, vp, vp],
         "ha_shard_bucket": [vp, i64, vp, c.c_int, vp, vp, vp],
         "ha_shard_route_f32ids": [vp, i64, vp, vp, c.c_int, vp, vp, vp],
         "ha_shard_route_u64ids": [vp, i64, vp, vp, c.c_int, vp, vp, vp],
@@ -320,6 +321,15 @@ def _declare(L):
         "ha_store_count_valid": [vp, i64, i64, vp, vp],
         "ha_cache_push_pull_begin": [vp, vp, c.c_int, i64, vp, c.c_int, i64, vp, vp, vp],
         "ha_cache_push_pull_finish": [vp, vp, vp],
+        "ha_cache_lookup_sum": [vp, vp, c.c_int, i64, i64, i64, vp, vp, vp],
+        "ha_cache_lookup_sum_presorted": [vp, vp, c.c_int, i64, i64, i64, vp, vp, vp],
+        "ha_cache_lookup_sum_finish": [vp, i64, i64, i64, vp, vp, vp],
+        "ha_cache_update_bags": [vp, vp, c.c_int, i64, vp, i64, i64, vp, vp],
+        "ha_cache_update_same_keys_bags": [vp, i64, vp, i64, i64, vp, vp],
+        "ha_cache_update_with_push_keys_bags": [vp, vp, c.c_int, i64, vp, c.c_int, i64, vp, i64, i64, vp, vp],
+        "ha_cache_push_pull_bags": [vp, vp, c.c_int, i64, i64, i64, vp, vp, vp, c.c_int, i64, vp, i64, i64, vp, vp],
+        "ha_cache_push_pull_begin_bags": [vp, vp, c.c_int, i64, vp, c.c_int, i64, vp, i64, i64, vp, vp, vp],
+        "ha_cache_push_pull_finish_sum": [vp, i64, i64, vp, vp, vp],
         "ha_store_serve_sync": [vp, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp],
         "ha_store_add_versions": [vp, i64, vp, vp, i64, vp],
         "ha_store_push_distinct": [vp, vp, i64, i64, vp, vp, vp, i64, vp],

@@ -192,16 +192,17 @@ class _CacheBase:
         else:
             self._remote.push(b["out_keys"][:bound], b["out_upd"][:bound], b["out_rows"][:bound])
 
-    def _lookup_remote(self, keys, dest):
+    def _lookup_remote(self, keys, dest, pooled=None):
+        """pooled = (nbags, bag or 0, offsets or None): `dest` is out [nbags, width], the rows arrive sum-pooled."""
         keep = []
         s = self._stream()
         with torch.cuda.stream(s):
             k, kind = self._keys(keys, keep)
             host_dest = None
-            if isinstance(dest, np.ndarray):
+            if pooled is None and isinstance(dest, np.ndarray):
                 host_dest = dest
                 dest = torch.empty((k.numel(), self._width), dtype=torch.float32, device=self.device)
-            assert dest.numel() == k.numel() * self._width and dest.dtype == torch.float32
+            assert pooled is not None or (dest.numel() == k.numel() * self._width and dest.dtype == torch.float32)
             if self._host_counts():
                 u = ctypes.c_int64(0)
                 check(self._L.ha_cache_lookup_begin(self._h, ctypes.c_void_p(k.data_ptr()), kind, k.numel(),
@@ -213,24 +214,38 @@ class _CacheBase:
                                                     ctypes.c_void_p(s.cuda_stream)), "ha_cache_lookup_begin")
                 self._sync_request(k.numel())
             self._evict_bound += k.numel()
-            check(self._L.ha_cache_lookup_finish(self._h, k.numel(), ctypes.c_void_p(dest.data_ptr()),
-                                                 ctypes.c_void_p(s.cuda_stream)), "ha_cache_lookup_finish")
+            if pooled is not None:
+                nbags, bag, offsets = pooled
+                check(self._L.ha_cache_lookup_sum_finish(
+                    self._h, k.numel(), nbags, bag, ctypes.c_void_p(offsets.data_ptr() if offsets is not None else None),
+                    ctypes.c_void_p(dest.data_ptr() if nbags else None), ctypes.c_void_p(s.cuda_stream)),
+                    "ha_cache_lookup_sum_finish")
+            else:
+                check(self._L.ha_cache_lookup_finish(self._h, k.numel(), ctypes.c_void_p(dest.data_ptr()),
+                                                     ctypes.c_void_p(s.cuda_stream)), "ha_cache_lookup_finish")
             # the plan of ha_cache_lookup_begin stays in the workspace: an update of the same key tensor can reuse it
             self._last_lookup = None if keep else _LookupMark(k)
             if self.perf_enabled:
                 self._perf_record(0)
-            w = Wait(s, keep + [k, dest])
+            w = Wait(s, keep + [k, dest, pooled[2] if pooled is not None else None])
             if host_dest is not None:
                 w._after = (lambda hd=host_dest, dd=dest: np.copyto(hd.reshape(dd.shape), dd.cpu().numpy()))
         return w
 
-    def _update_remote(self, keys, grads, push_keys, same_as_lookup=False):
+    def _update_remote(self, keys, grads, push_keys, same_as_lookup=False, pooled=None):
+        """pooled = (nbags, bag or 0, bag_of or None): `grads` is the pooled gradient bag_grads [nbags, width]."""
         keep = []
         s = self._stream()
+        vp = ctypes.c_void_p
         with torch.cuda.stream(s):
             k, kind = self._keys(keys, keep)
             g = self._grads(grads, keep)
-            assert g.numel() == k.numel() * self._width
+            assert g.numel() == (k.numel() if pooled is None else pooled[0]) * self._width
+            if pooled is not None:
+                nbags, bag, bag_of = pooled
+                keep.append(bag_of)
+                tail = (vp(g.data_ptr() if nbags else None), nbags, bag, vp(bag_of.data_ptr() if bag_of is not None else None),
+                        vp(s.cuda_stream))
             same = bool(same_as_lookup) and k.numel() > 0 and _is_marked(self._last_lookup, k)
             if same_as_lookup and not same:
                 raise ValueError("same_as_lookup=True, but no embedding_lookup of this key tensor precedes")
@@ -238,7 +253,16 @@ class _CacheBase:
             bound = None if self._host_counts() else self._outbox_bound(k.numel())
             check(self._L.ha_cache_outbox_pad(self._h, bound or 0), "ha_cache_outbox_pad")
             fused0 = int(self._L.ha_cache_fused_updates(self._h))
-            if push_keys is None and same:       # the lookup's index plan is still in the workspace
+            if pooled is not None and push_keys is None and same:
+                check(self._L.ha_cache_update_same_keys_bags(self._h, k.numel(), *tail), "ha_cache_update_same_keys_bags")
+            elif pooled is not None and push_keys is None:
+                check(self._L.ha_cache_update_bags(self._h, vp(k.data_ptr()), kind, k.numel(), *tail), "ha_cache_update_bags")
+            elif pooled is not None:
+                pk, pkind = self._keys(push_keys, keep)
+                check(self._L.ha_cache_update_with_push_keys_bags(self._h, vp(k.data_ptr()), kind, k.numel(), vp(pk.data_ptr()),
+                                                                  pkind, pk.numel(), *tail),
+                      "ha_cache_update_with_push_keys_bags")
+            elif push_keys is None and same:       # the lookup's index plan is still in the workspace
                 check(self._L.ha_cache_update_same_keys(self._h, k.numel(), ctypes.c_void_p(g.data_ptr()),
                                                         ctypes.c_void_p(s.cuda_stream)), "ha_cache_update_same_keys")
             elif push_keys is None:
@@ -259,28 +283,45 @@ class _CacheBase:
                 self._perf_record(1)
             return Wait(s, keep + [k, g])
 
-    def _push_pull_remote(self, pullkeys, dest, pushkeys, grads):
-        keep = []
+    def _push_pull_remote(self, pullkeys, dest, pushkeys, grads, pull_pooled=None, push_pooled=None):
+        """pull_pooled = (nbags, bag or 0, offsets or None): `dest` is out [nbags, width]; push_pooled = (nbags, bag or 0, bag_of
+        or None): `grads` is bag_grads [nbags, width]."""
+        keep = [x for x in (pull_pooled or ())[2:] + (push_pooled or ())[2:] if x is not None]
         self._last_lookup = None
         s = self._stream()
+        vp = ctypes.c_void_p
         with torch.cuda.stream(s):
             pk, pkind = self._keys(pullkeys, keep)
             sk, skind = self._keys(pushkeys, keep)
             g = self._grads(grads, keep)
-            assert dest.is_cuda and dest.dtype == torch.float32 and dest.numel() == pk.numel() * self._width
+            assert dest.is_cuda and dest.dtype == torch.float32 and \
+                dest.numel() == (pk.numel() if pull_pooled is None else pull_pooled[0]) * self._width
             hc = self._host_counts()
             bound = None if hc else self._outbox_bound(sk.numel())
             check(self._L.ha_cache_outbox_pad(self._h, bound or 0), "ha_cache_outbox_pad")
             u = ctypes.c_int64(0)
-            check(self._L.ha_cache_push_pull_begin(self._h, ctypes.c_void_p(pk.data_ptr()), pkind, pk.numel(),
-                                                   ctypes.c_void_p(sk.data_ptr()), skind, sk.numel(),
-                                                   ctypes.c_void_p(g.data_ptr()), ctypes.byref(u) if hc else None,
-                                                   ctypes.c_void_p(s.cuda_stream)), "ha_cache_push_pull_begin")
+            if push_pooled is not None:
+                nbq, bagq, bag_of = push_pooled
+                check(self._L.ha_cache_push_pull_begin_bags(
+                    self._h, vp(pk.data_ptr()), pkind, pk.numel(), vp(sk.data_ptr()), skind, sk.numel(),
+                    vp(g.data_ptr() if nbq else None), nbq, bagq, vp(bag_of.data_ptr() if bag_of is not None else None),
+                    ctypes.byref(u) if hc else None, vp(s.cuda_stream)), "ha_cache_push_pull_begin_bags")
+            else:
+                check(self._L.ha_cache_push_pull_begin(self._h, ctypes.c_void_p(pk.data_ptr()), pkind, pk.numel(),
+                                                       ctypes.c_void_p(sk.data_ptr()), skind, sk.numel(),
+                                                       ctypes.c_void_p(g.data_ptr()), ctypes.byref(u) if hc else None,
+                                                       ctypes.c_void_p(s.cuda_stream)), "ha_cache_push_pull_begin")
             self._push_outbox(s, bound)          # the server pushes before it syncs
             self._sync_request(int(u.value) if hc else pk.numel())
             self._evict_bound = pk.numel()       # the pull phase's evictions stay pending until the next update
-            check(self._L.ha_cache_push_pull_finish(self._h, ctypes.c_void_p(dest.data_ptr()),
-                                                    ctypes.c_void_p(s.cuda_stream)), "ha_cache_push_pull_finish")
+            if pull_pooled is not None:
+                nbp, bagp, offsets = pull_pooled
+                check(self._L.ha_cache_push_pull_finish_sum(
+                    self._h, nbp, bagp, vp(offsets.data_ptr() if offsets is not None else None),
+                    vp(dest.data_ptr() if nbp else None), vp(s.cuda_stream)), "ha_cache_push_pull_finish_sum")
+            else:
+                check(self._L.ha_cache_push_pull_finish(self._h, ctypes.c_void_p(dest.data_ptr()),
+                                                        ctypes.c_void_p(s.cuda_stream)), "ha_cache_push_pull_finish")
             return Wait(s, keep + [pk, sk, g, dest])
 
     # ---- properties of the reference ----------------------------------------------------------------------
@@ -957,6 +998,154 @@ class _CacheBase:
                                              ctypes.c_void_p(s.cuda_stream)), "ha_cache_push_pull")
             return Wait(s, keep + [pk, sk, g, dest])
 
+    # ---- sum-pooled access, call by call (csrc/cache.hip: cache_lookup_rows_sum_kernel, ha_apply_mapped2_bags): the callers the
+    # planned flow does not reach -- a remote store, LFU / LFUOpt on the asp schedule, no ids a block ahead, push plans
+    @staticmethod
+    def _numel(who, keys):
+        if isinstance(keys, np.ndarray):
+            return int(keys.size)
+        if not torch.is_tensor(keys):
+            raise TypeError("%s: keys must be a tensor or a numpy array" % who)
+        return int(keys.numel())
+
+    def embedding_lookup_sum(self, keys, out, bag=None, offsets=None):
+        """embedding_lookup delivered SUM-POOLED: out[b,:] = ((0 + r_lo) + r_lo+1) + ... over the rows of bag b's keys in
+        position order -- bit for bit embedding_lookup followed by ops.embedding_lookup_sum over its rows, which are never
+        written; the cache is left as that lookup leaves it (lines, versions, perf record, the plan an update with
+        same_as_lookup=True reuses).  out: float32 device tensor [nbags, width]; bag: fixed bags of `bag` keys (nbags * bag ==
+        n), or offsets: int64 device tensor [nbags + 1] (offsets[0] = 0, offsets[nbags] = n, non-decreasing; clamped to [0, n])."""
+        who = "embedding_lookup_sum"
+        nbags = self._pooled_args(who, "out", out, self._numel(who, keys), bag, offsets, "offsets")
+        bag = int(bag) if bag is not None else 0
+        if self._remote is not None:
+            return self._lookup_remote(keys, out, (nbags, bag, offsets))
+        keep = []
+        s = self._stream()
+        with torch.cuda.stream(s):
+            k, kind = self._keys(keys, keep)
+            lookup = self._L.ha_cache_lookup_sum
+            if self._ahead_ring:
+                if _is_marked(self._ahead_ring[0], k):
+                    lookup = self._L.ha_cache_lookup_sum_presorted
+                    self._ahead_ring.pop(0)
+                else:           # not the batch that was announced: the rest of the block sorts by itself
+                    self._drop_ahead_ring()
+            elif self._ahead is not None and _is_marked(self._ahead, k):
+                lookup, self._ahead = self._L.ha_cache_lookup_sum_presorted, None
+            check(lookup(self._h, ctypes.c_void_p(k.data_ptr()), kind, k.numel(), nbags, bag,
+                         ctypes.c_void_p(offsets.data_ptr() if offsets is not None else None),
+                         ctypes.c_void_p(out.data_ptr() if nbags else None), ctypes.c_void_p(s.cuda_stream)),
+                  "ha_cache_lookup_sum")
+            self._last_lookup = None if keep else _LookupMark(k)
+            if self.perf_enabled:
+                self._perf_record(0)
+            return Wait(s, keep + [k, out, offsets])
+
+    def embedding_update_bags(self, keys, bag_grads, bag=None, bag_of=None, same_as_lookup=False):
+        """embedding_update from the POOLED gradient bag_grads [nbags, width]: bit for bit embedding_update(keys, bag_grads[bag
+        of every key]) without the expanded tensor.  bag: fixed bags of `bag` keys, or bag_of: int32 device tensor [n], the bag
+        of every key (ops.bag_of(offsets, n)).  same_as_lookup: as embedding_update; the lookup may have been either form."""
+        who = "embedding_update_bags"
+        nbags = self._pooled_args(who, "bag_grads", bag_grads, self._numel(who, keys), bag, bag_of, "bag_of")
+        bag = int(bag) if bag is not None else 0
+        if self._remote is not None:
+            return self._update_remote(keys, bag_grads, None, same_as_lookup, (nbags, bag, bag_of))
+        keep = []
+        s = self._stream()
+        vp = ctypes.c_void_p
+        with torch.cuda.stream(s):
+            k, kind = self._keys(keys, keep)
+            same = bool(same_as_lookup) and k.numel() > 0 and _is_marked(self._last_lookup, k)
+            if same_as_lookup and not same:
+                raise ValueError("same_as_lookup=True, but no embedding_lookup of this key tensor precedes")
+            self._last_lookup = None
+            tail = (vp(bag_grads.data_ptr() if nbags else None), nbags, bag,
+                    vp(bag_of.data_ptr() if bag_of is not None else None), vp(s.cuda_stream))
+            if same:
+                check(self._L.ha_cache_update_same_keys_bags(self._h, k.numel(), *tail), "ha_cache_update_same_keys_bags")
+            else:
+                check(self._L.ha_cache_update_bags(self._h, vp(k.data_ptr()), kind, k.numel(), *tail), "ha_cache_update_bags")
+            if self.perf_enabled:
+                self._perf_record(1)
+            return Wait(s, keep + [k, bag_grads, bag_of])
+
+    def embedding_update_with_push_keys_bags(self, keys, push_keys, bag_grads, bag=None, bag_of=None):
+        """embedding_update_with_push_keys from the pooled gradient bag_grads [nbags, width] (see embedding_update_bags)."""
+        who = "embedding_update_with_push_keys_bags"
+        nbags = self._pooled_args(who, "bag_grads", bag_grads, self._numel(who, keys), bag, bag_of, "bag_of")
+        bag = int(bag) if bag is not None else 0
+        if self._remote is not None:
+            return self._update_remote(keys, bag_grads, push_keys, False, (nbags, bag, bag_of))
+        self._last_lookup = None
+        keep = []
+        s = self._stream()
+        vp = ctypes.c_void_p
+        with torch.cuda.stream(s):
+            k, kind = self._keys(keys, keep)
+            pk, pkind = self._keys(push_keys, keep)
+            check(self._L.ha_cache_update_with_push_keys_bags(
+                self._h, vp(k.data_ptr()), kind, k.numel(), vp(pk.data_ptr()), pkind, pk.numel(),
+                vp(bag_grads.data_ptr() if nbags else None), nbags, bag, vp(bag_of.data_ptr() if bag_of is not None else None),
+                vp(s.cuda_stream)), "ha_cache_update_with_push_keys_bags")
+            if self.perf_enabled:
+                self._perf_record(1)
+            return Wait(s, keep + [k, pk, bag_grads, bag_of])
+
+    def embedding_push_pull_bags(self, pullkeys, out, pushkeys, bag_grads, bag=None, pull_offsets=None, push_bag_of=None):
+        """embedding_push_pull SUM-POOLED on both sides: the pooled gradient bag_grads [nbags, width] of pushkeys is accumulated
+        and pushed, then pullkeys are pulled pooled into out [nbags, width] -- bit for bit the unpooled call with
+        ops.embedding_lookup_sum over its rows and the expanded gradient; no [n, width] tensor on either side.  bag: fixed bags
+        of `bag` keys, for every side that has no ragged description; pull_offsets: int64 device tensor [nbags + 1] of the pull
+        keys; push_bag_of: int32 device tensor [n] of the push keys.  (One side only: embedding_push_pull_bags_side.)"""
+        who = "embedding_push_pull_bags"
+        if bag is not None and pull_offsets is not None and push_bag_of is not None:
+            raise ValueError("%s: give exactly one of bag and the ragged description per side: bag describes no side here" % who)
+        bag_p = bag if pull_offsets is None else None
+        bag_q = bag if push_bag_of is None else None
+        nbp = self._pooled_args(who, "out", out, self._numel(who, pullkeys), bag_p, pull_offsets, "pull_offsets")
+        nbq = self._pooled_args(who, "bag_grads", bag_grads, self._numel(who, pushkeys), bag_q, push_bag_of, "push_bag_of")
+        return self._push_pull_sides(pullkeys, out, pushkeys, bag_grads,
+                                     (nbp, int(bag_p) if bag_p is not None else 0, pull_offsets),
+                                     (nbq, int(bag_q) if bag_q is not None else 0, push_bag_of))
+
+    def embedding_push_pull_bags_side(self, pullkeys, dest, pushkeys, grads, pull_bag=None, pull_offsets=None, push_bag=None,
+                                      push_bag_of=None):
+        """embedding_push_pull with the sides pooled INDEPENDENTLY: the pull side is pooled when pull_bag or pull_offsets is
+        given (`dest` is then out [nbags, width]), the push side when push_bag or push_bag_of is (`grads` is then bag_grads
+        [nbags, width]); a side with neither is the unpooled call's."""
+        who = "embedding_push_pull_bags_side"
+        pull_pooled = push_pooled = None
+        if pull_bag is not None or pull_offsets is not None:
+            nbp = self._pooled_args(who, "dest", dest, self._numel(who, pullkeys), pull_bag, pull_offsets, "pull_offsets")
+            pull_pooled = (nbp, int(pull_bag) if pull_bag is not None else 0, pull_offsets)
+        if push_bag is not None or push_bag_of is not None:
+            nbq = self._pooled_args(who, "grads", grads, self._numel(who, pushkeys), push_bag, push_bag_of, "push_bag_of")
+            push_pooled = (nbq, int(push_bag) if push_bag is not None else 0, push_bag_of)
+        return self._push_pull_sides(pullkeys, dest, pushkeys, grads, pull_pooled, push_pooled)
+
+    def _push_pull_sides(self, pullkeys, dest, pushkeys, grads, pull_pooled, push_pooled):
+        if self._remote is not None:
+            return self._push_pull_remote(pullkeys, dest, pushkeys, grads, pull_pooled, push_pooled)
+        self._last_lookup = None
+        keep = []
+        s = self._stream()
+        vp = ctypes.c_void_p
+        with torch.cuda.stream(s):
+            pk, pkind = self._keys(pullkeys, keep)
+            sk, skind = self._keys(pushkeys, keep)
+            g = self._grads(grads, keep)
+            nbp, bagp, offsets = pull_pooled if pull_pooled is not None else (-1, 0, None)
+            nbq, bagq, bag_of = push_pooled if push_pooled is not None else (-1, 0, None)
+            assert dest.is_cuda and dest.dtype == torch.float32 and \
+                dest.numel() == (pk.numel() if nbp < 0 else nbp) * self._width
+            assert g.is_cuda and g.numel() == (sk.numel() if nbq < 0 else nbq) * self._width
+            check(self._L.ha_cache_push_pull_bags(
+                self._h, vp(pk.data_ptr()), pkind, pk.numel(), nbp, bagp, vp(offsets.data_ptr() if offsets is not None else None),
+                vp(dest.data_ptr() if dest.numel() else None), vp(sk.data_ptr()), skind, sk.numel(),
+                vp(g.data_ptr() if g.numel() else None), nbq, bagq, vp(bag_of.data_ptr() if bag_of is not None else None),
+                vp(s.cuda_stream)), "ha_cache_push_pull_bags")
+            return Wait(s, keep + [pk, sk, g, dest, offsets, bag_of])
+
     embedding_push_pull_raw = embedding_push_pull
 
     # the *_raw spellings of the reference take addresses; here they take the tensors themselves
@@ -1192,6 +1381,31 @@ class CacheSparseTable:
 
     def embedding_update_with_push_keys(self, keys, push_keys, grads, sync=False):
         return self._finish(self.cache.embedding_update_with_push_keys(keys, push_keys, grads), sync)
+
+    # sum-pooled access, call by call (see _CacheBase)
+    def embedding_lookup_sum(self, keys, out, bag=None, offsets=None, sync=False):
+        if isinstance(keys, tuple):
+            keys = keys[0]
+        return self._finish(self.cache.embedding_lookup_sum(keys, out, bag=bag, offsets=offsets), sync)
+
+    def embedding_update_bags(self, keys, bag_grads, bag=None, bag_of=None, same_as_lookup=False, sync=False):
+        return self._finish(self.cache.embedding_update_bags(keys, bag_grads, bag=bag, bag_of=bag_of,
+                                                             same_as_lookup=same_as_lookup), sync)
+
+    def embedding_update_with_push_keys_bags(self, keys, push_keys, bag_grads, bag=None, bag_of=None, sync=False):
+        return self._finish(self.cache.embedding_update_with_push_keys_bags(keys, push_keys, bag_grads, bag=bag, bag_of=bag_of),
+                            sync)
+
+    def embedding_push_pull_bags(self, pullkeys, out, pushkeys, bag_grads, bag=None, pull_offsets=None, push_bag_of=None,
+                                 sync=False):
+        return self._finish(self.cache.embedding_push_pull_bags(pullkeys, out, pushkeys, bag_grads, bag=bag,
+                                                                pull_offsets=pull_offsets, push_bag_of=push_bag_of), sync)
+
+    def embedding_push_pull_bags_side(self, pullkeys, dest, pushkeys, grads, pull_bag=None, pull_offsets=None, push_bag=None,
+                                      push_bag_of=None, sync=False):
+        return self._finish(self.cache.embedding_push_pull_bags_side(pullkeys, dest, pushkeys, grads, pull_bag=pull_bag,
+                                                                     pull_offsets=pull_offsets, push_bag=push_bag,
+                                                                     push_bag_of=push_bag_of), sync)
 
     def embedding_push_pull(self, pullkeys, dest, pushkeys, grads, sync=False):
         return self._finish(self.cache.embedding_push_pull(pullkeys, dest, pushkeys, grads), sync)

@@ -35,6 +35,7 @@
 // The batch index plan (plan.hip) supplies sorted unique keys / inverse / counts; occurrence-order
 // accumulation and the ordered server `+=` reuse the apply kernels (scatter_dev.h, ha_apply_mapped).
 #include "cache_dev.h"
+#include "scatter_dev.h"
 
 extern "C" int ha_apply_mapped(float *dst, int64_t dst_rows, int64_t width,
                                const void *plan_ws, int64_t n, const float *src,
@@ -45,6 +46,8 @@ extern "C" int ha_apply_mapped2(float *dst, int64_t dst_rows, float *dst2, int64
                                 const void *plan_ws, int64_t n, const float *src, float lr,
                                 const int32_t *rowmap, const int32_t *rowmap2,
                                 const uint8_t *dst_init, ha_stream_t stream);
+extern "C" int ha_gather_sum_u32keys(const float *rows_buf, int64_t rows, int64_t width, const uint32_t *keys, int64_t n,
+                                     int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
 
 namespace ha {
 
@@ -1191,7 +1194,174 @@ __global__ __launch_bounds__(1024) void cache_lookup_rows_kernel(
         c.line[s].version = c.remote ? c.inbox_ver[u] : c.srv_ver[lk];
 }
 
+// The sum-pooled twin of cache_lookup_rows_kernel (ha_cache_lookup_sum*): out[b,:] = ((0.0f + r_lo) + r_lo+1) + ... over the rows
+// of bag b's occurrences in position order, one __fadd_rn per term -- what cache_lookup_rows_kernel followed by ha_gather_sum
+// over the ids 0 .. n-1 gives, bit for bit; the [n, width] rows are never written.  The mapping is bag_sum_kernel's (bagsum.hip):
+// one wave per (bag, column slice), a bag split over waves by COLUMNS only, lane l of a block of 64 positions fetches what its
+// occurrence needs, the row pointers are broadcast with v_readlane and ROWS clamped row loads are in flight before the first add.
+// Every decision comes from the per-unique-key arrays the bookkeeping left, reached through the batch's index plan: occurrence
+// j is key u = inverse[j] in slot uslot[u], pulled when data_row[u] != 0 (remote mode: the owner's inbox_pull).
+// One writer.  A line that is not pulled is read from its data row, which nobody writes.  A pulled key is read by EVERY wave
+// from the store (the table row, or the inbox row in remote mode; + the line's gradient row, Line::addup), never from the data
+// row being refreshed; the waves whose bag holds the key's FIRST occurrence (perm[seg[u]], the sort is stable) store the
+// refreshed row, each its own column slice, and the slice-0 wave of them writes the line's version.  Bags are disjoint ranges
+// of positions, so that is one wave per slice.
+// Every index is checked before an address is formed from it; an occurrence that fails a check adds a zero row and refreshes
+// nothing.  Victim scan, insert + eviction and the report follow in a launch of their own (the 1024-thread role of
+// cache_lookup_rows_kernel): this kernel's workgroups are 256 threads, so that 32 row requests of 16 bytes per lane fit the
+// register file without scratch.
+template <int VEC>
+struct RowsSumVec;
+template <>
+struct RowsSumVec<1> {
+    typedef float T;
+    static __device__ __forceinline__ float get(const T &v, int) { return v; }
+    static __device__ __forceinline__ void set(T &v, int, float x) { v = x; }
+};
+template <>
+struct RowsSumVec<4> {
+    typedef float4v T;
+    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
+    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
+};
+constexpr int kRowsSumWaves = 4;     // waves per workgroup
+constexpr int kRsOk = 1, kRsGrad = 2, kRsHead = 4;
+
+template <int VEC, int ROWS>
+__global__ __launch_bounds__(kRowsSumWaves *kWave) void cache_lookup_rows_sum_kernel(
+    Cache c, const uint32_t *__restrict__ uniq, const int32_t *__restrict__ inverse, const int32_t *__restrict__ seg,
+    const int32_t *__restrict__ perm, long long n, long long bag, const int64_t *__restrict__ offsets, long long nbags,
+    uint32_t nslice, float *__restrict__ out) {
+    typedef typename RowsSumVec<VEC>::T V;
+    typedef const V __attribute__((address_space(1))) *GlobalV;
+    const int lane = lane_id();
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kRowsSumWaves + (threadIdx.x >> 6);   // wave-uniform
+    if (item >= static_cast<uint64_t>(nbags) * nslice)
+        return;
+    const long long b = static_cast<long long>(item / nslice);
+    const uint32_t sl = static_cast<uint32_t>(item - static_cast<uint64_t>(b) * nslice);
+    long long lo, hi;
+    if (offsets != nullptr) {
+        lo = offsets[b];
+        hi = offsets[b + 1];
+        lo = lo < 0 ? 0 : (lo > n ? n : lo);
+        hi = hi < lo ? lo : (hi > n ? n : hi);
+    } else {
+        lo = b * bag;
+        hi = lo + bag;      // (n == nbags * bag: checked by the host)
+    }
+    const uint32_t width = static_cast<uint32_t>(c.width);
+    const uint32_t col = (sl * kWave + lane) * VEC;
+    const bool live = col < width;       // (VEC > 1: width % VEC == 0, so a live lane's VEC columns all exist)
+    const uint32_t lcol = live ? col : 0;
+    V acc;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+        RowsSumVec<VEC>::set(acc, k, 0.f);
+    for (long long j0 = lo; j0 < hi; j0 += kWave) {
+        const int cnt = static_cast<int>(hi - j0 < kWave ? hi - j0 : kWave);      // positions of this block (wave-uniform)
+        const bool mine = lane < cnt;
+        const long long j = j0 + (mine ? lane : cnt - 1);                          // lo <= j < hi <= n
+        // ---- the occurrence's key (every index is checked before an address is formed from it)
+        const int u = inverse[j];
+        const bool u_ok = u >= 0 && u < n;
+        const int uu = u_ok ? u : 0;
+        const int s = c.uslot[uu];
+        const bool pull = c.data_row[uu] != 0;
+        const int sg = seg[uu];
+        const long long lk = static_cast<long long>(uniq[uu]) - c.row_start;
+        const int ix = (c.remote && pull) ? c.inbox_idx[uu] : 0;
+        const bool src_ok = !pull || (c.remote ? (ix >= 0 && ix < c.nmax) : (lk >= 0 && lk < c.store_rows));
+        const bool ok = u_ok && s >= 0 && s < c.S && sg >= 0 && sg < n && src_ok;
+        const bool head = ok && mine && pull && static_cast<long long>(perm[ok ? sg : 0]) == j;
+        const bool hg = ok && pull && c.hasgrad[s] != 0;
+        if (head && sl == 0)
+            c.line[s].version = c.remote ? c.inbox_ver[uu] : c.srv_ver[lk];
+        const uint64_t loff = static_cast<uint64_t>(ok ? s : 0) * width;      // float offset of the line's rows
+        const float *src = !ok ? c.data
+                           : !pull ? c.data + loff
+                           : c.remote ? c.inbox_rows + static_cast<uint64_t>(ix) * width
+                                      : c.table + static_cast<uint64_t>(lk) * width;
+        const uint64_t sa = reinterpret_cast<uint64_t>(src);
+        const int src_lo = static_cast<int>(static_cast<uint32_t>(sa)), src_hi = static_cast<int>(static_cast<uint32_t>(sa >> 32));
+        const int lof_lo = static_cast<int>(static_cast<uint32_t>(loff)), lof_hi = static_cast<int>(static_cast<uint32_t>(loff >> 32));
+        const int rf = (ok ? kRsOk : 0) | (hg ? kRsGrad : 0) | (head ? kRsHead : 0);
+        for (int r0 = 0; r0 < cnt; r0 += ROWS) {
+            V x[ROWS];
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const int tt = r0 + t < cnt ? r0 + t : cnt - 1;
+                const uint64_t a = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(src_hi, tt))) << 32) |
+                                   static_cast<uint32_t>(__builtin_amdgcn_readlane(src_lo, tt));
+                // (a pointer rebuilt from two registers: told to be a GLOBAL one, or the loads would be flat_load)
+                x[t] = *(GlobalV)(a + static_cast<uint64_t>(lcol) * sizeof(float));
+            }
+            // every request of the round is issued before the first add (see bag_sum_kernel)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const bool in = r0 + t < cnt;                                     // wave-uniform
+                const int f = __builtin_amdgcn_readlane(rf, in ? r0 + t : 0);     // wave-uniform
+                V xv = x[t];
+                if (in && (f & (kRsGrad | kRsHead))) {      // a pulled line with a gradient buffer, or the key's head: rare
+                    const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(lof_hi, r0 + t))) << 32) |
+                                       static_cast<uint32_t>(__builtin_amdgcn_readlane(lof_lo, r0 + t));
+                    if (f & kRsGrad) {
+                        const V g = *reinterpret_cast<const V *>(c.grad + o + lcol);
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k)
+                            RowsSumVec<VEC>::set(xv, k, __fadd_rn(RowsSumVec<VEC>::get(xv, k), RowsSumVec<VEC>::get(g, k)));   // data += grad
+                    }
+                    if ((f & kRsHead) && live)
+                        *reinterpret_cast<V *>(c.data + o + col) = xv;
+                }
+                const bool rok = (f & kRsOk) != 0;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float a = RowsSumVec<VEC>::get(acc, k);
+                    const float sum = __fadd_rn(a, rok ? RowsSumVec<VEC>::get(xv, k) : 0.f);
+                    RowsSumVec<VEC>::set(acc, k, in ? sum : a);
+                }
+            }
+        }
+    }
+    // the pooled rows are consumed by another kernel (the dense tower): written around the L2, as bag_sum_kernel's
+    if (live)
+        __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
+}
+
+// per-occurrence slot of a push-pull's pull batch (0xFFFFFFFF: no line -- a zero row of the sum): the ids of the bag sum over
+// the cache's data rows that takes cache_dest_kernel's place in a pooled push-pull
+__global__ __launch_bounds__(256) void cache_slot_map_kernel(Cache c, const int32_t *__restrict__ inverse, long long n,
+                                                             uint32_t *__restrict__ map) {
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+        const int u = inverse[i];
+        const int s = (u >= 0 && u < n) ? c.uslot[u] : -1;
+        map[i] = (s >= 0 && s < c.S) ? static_cast<uint32_t>(s) : 0xFFFFFFFFu;
+    }
+}
+
 // ---- update ----------------------------------------------------------------------------------------
+// Line::accumulate from POOLED gradients: apply_mapped2_kernel (scatter.hip: two destinations, one pass -- the gradient buffer
+// and the data row) in its BAGS instantiation -- the source row of occurrence i is its bag's row of bag_grads, i / valdiv in
+// registers for fixed bags, valmap[i] = bag_of[i] for ragged ones.  The same runs take the same chain (short, medium and the
+// cooperative long-run path) over the same values as the unpooled kernel on the expanded [n, width] gradient: the same bits in
+// both destinations.  It lives here, beside its only callers, so that the apply kernels' own translation unit is untouched.
+template <int VEC, bool FIXED>
+__global__ __launch_bounds__(1024, 8) void apply_mapped2_bags_kernel(
+    float *__restrict__ dst, uint64_t dst_rows, int width,
+    const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm,
+    const int32_t *__restrict__ upos, int n, const float *__restrict__ bag_grads,
+    float lr, ApplyMaps maps) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
+    if (FIXED)
+        maps.valmap = nullptr;
+    else
+        maps.valdiv = 0;
+    apply_body<kModeSgd, VEC, true, kHandNone, true>(dst, dst_rows, width, sorted, perm, upos, n, bag_grads, lr, blockIdx.x,
+                                                     s_apply, nullptr, maps);
+}
+
 // rows for the two accumulate passes: grad row = slot (every line), data row = slot for lines with data
 __device__ __forceinline__ void cache_update_rows_body(const CacheCtl *ctl, const Cache &c, int tid0, int nthr) {
     const int U = static_cast<int>(ctl->U);
@@ -1920,6 +2090,115 @@ static int cache_evict_mode(const ha_cache *h, int64_t n, int probed) {
     return 1;
 }
 
+// ha_apply_mapped2 (scatter.hip) with src = bag_grads[nbags, width] expanded to [n, width], without the expanded tensor; the
+// argument rules are bags_args_ok's (scatter.hip), everything checked before any device access.  The tolerance modes do not reach
+// a two-destination apply (its runs are always the serial chain), so there is nothing else to match.
+extern "C" int ha_apply_mapped2_bags(float *dst, int64_t dst_rows, float *dst2, int64_t width, const void *plan_ws, int64_t n,
+                                     const float *bag_grads, float lr, const int32_t *rowmap, const int32_t *rowmap2,
+                                     int64_t bag, const int32_t *bag_of, const uint8_t *dst_init, ha_stream_t stream) {
+    const char *what = "ha_apply_mapped2_bags";
+    HA_REQUIRE(n >= 0 && dst_rows >= 0 && width >= 1 && width < (1 << 30) && n < (1ll << 31) && bag >= 0, "%s: bad sizes", what);
+    HA_REQUIRE((bag >= 1) != (bag_of != nullptr), "%s: give exactly one of bag >= 1 and bag_of (bag=%ld)", what, (long)bag);
+    HA_REQUIRE(bag_of != nullptr || (bag < (1ll << 31) && n % bag == 0), "%s: n=%ld is not a multiple of bag=%ld", what, (long)n,
+               (long)bag);
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(dst && dst2 && plan_ws && bag_grads && rowmap && rowmap2, "%s: null pointer", what);
+    const bool fixed = bag_of == nullptr;
+    ha_plan_view v;
+    if (ha_plan_view_of(const_cast<void *>(plan_ws), n, &v) != 0)
+        return -1;
+    const unsigned blocks = static_cast<unsigned>((n + kPosPerBlock - 1) / kPosPerBlock);
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(dst2) % 16 == 0) && (reinterpret_cast<uintptr_t>(bag_grads) % 16 == 0);
+    ApplyMaps maps{rowmap, bag_of, dst_init, dst2, rowmap2};
+    maps.valdiv = fixed ? static_cast<int>(bag) : 0;
+    static DeviceOnce lds_allowed;
+    if (lds_allowed.run([]() -> int {
+            HA_ALLOW_LDS((apply_mapped2_bags_kernel<4, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_mapped2_bags_kernel<4, false>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_mapped2_bags_kernel<1, true>), kApplyLdsBytes);
+            HA_ALLOW_LDS((apply_mapped2_bags_kernel<1, false>), kApplyLdsBytes);
+            return 0;
+        }))
+        return -1;
+#define HA_M2BAGS_CASE(V, F)                                                                                              \
+    hipLaunchKernelGGL((apply_mapped2_bags_kernel<V, F>), dim3(blocks), dim3(1024), kApplyLdsBytes, as_stream(stream), dst, \
+                       (uint64_t)dst_rows, (int)width, v.sorted, v.perm, v.upos, (int)n, bag_grads, lr, maps)
+    if (vec_ok && fixed) HA_M2BAGS_CASE(4, true);
+    else if (vec_ok) HA_M2BAGS_CASE(4, false);
+    else if (fixed) HA_M2BAGS_CASE(1, true);
+    else HA_M2BAGS_CASE(1, false);
+#undef HA_M2BAGS_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- sum-pooled access, call by call (ha_cache_lookup_sum*, ha_cache_update*_bags, ha_cache_push_pull*_bags) ------------------
+// the pooled delivery of a lookup: out[nbags, width], fixed bags of `bag` ids or ragged ones by offsets[nbags + 1]
+struct SumOut {
+    int64_t nbags, bag;
+    const int64_t *offsets;
+    float *out;
+};
+// the pooled gradient of an update: bag_grads[nbags, width] arrives as the call's `grads`; fixed bags or bag_of[n]
+struct BagSrc {
+    int64_t nbags, bag;
+    const int32_t *bag_of;
+};
+// ha_cache_lookup_sum_planned's rules; everything here precedes any device access
+static int sum_args_ok(const char *who, int64_t n, const SumOut &so) {
+    HA_REQUIRE(n >= 0 && n < (1ll << 31) && so.nbags >= 0 && so.nbags < (1ll << 31) && so.bag >= 0,
+               "%s: bad sizes n=%ld nbags=%ld bag=%ld", who, (long)n, (long)so.nbags, (long)so.bag);
+    HA_REQUIRE((so.bag >= 1) != (so.offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld, offsets %s)", who,
+               (long)so.bag, so.offsets ? "given" : "null");
+    HA_REQUIRE(so.offsets != nullptr || (n % so.bag == 0 && n / so.bag == so.nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids",
+               who, (long)n, (long)so.nbags, (long)so.bag);
+    HA_REQUIRE(n == 0 || so.nbags >= 1, "%s: %ld ids in no bag", who, (long)n);
+    HA_REQUIRE(so.nbags == 0 || so.out, "%s: null output", who);
+    return 0;
+}
+// bags_args_ok's rules (scatter.hip) and the pooled gradient's shape
+static int bag_src_ok(const char *who, int64_t n, const float *bag_grads, const BagSrc &bs) {
+    HA_REQUIRE(n >= 0 && n < (1ll << 31) && bs.nbags >= 0 && bs.nbags < (1ll << 31) && bs.bag >= 0,
+               "%s: bad sizes n=%ld nbags=%ld bag=%ld", who, (long)n, (long)bs.nbags, (long)bs.bag);
+    HA_REQUIRE((bs.bag >= 1) != (bs.bag_of != nullptr), "%s: give exactly one of bag >= 1 and bag_of (bag=%ld)", who, (long)bs.bag);
+    HA_REQUIRE(bs.bag_of != nullptr || (bs.bag < (1ll << 31) && n % bs.bag == 0 && n / bs.bag == bs.nbags),
+               "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", who, (long)n, (long)bs.nbags, (long)bs.bag);
+    HA_REQUIRE(n == 0 || (bs.nbags >= 1 && bag_grads), "%s: %ld ids, but no bags or a null bag_grads", who, (long)n);
+    return 0;
+}
+
+// The row launch of a pooled lookup and, behind it (the reference's order: the rows are delivered before the policy inserts and
+// evicts, cache.cc:95-104), the rest of the bookkeeping when the bookkeeping kernel deferred it (evb != 0): the 1024-thread role
+// of cache_lookup_rows_kernel, launched as that workgroup alone.  `c`: the view whose data_row holds the pull decisions.
+// 16-byte path: width % 4 == 0 and every row base aligned; 64 x 4 floats per slice.  Rows per round by the (mean) bag size.
+static int lookup_sum_rows(const Cache &c, const PlanPtrs &p, int64_t n, const SumOut &so, int evb, hipStream_t s, const char *who) {
+    if (so.nbags > 0) {
+        const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(so.out) % 16 == 0) &&
+                            (c.remote || reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
+        const int vec = vec_ok ? 4 : 1;
+        const uint32_t nslice = static_cast<uint32_t>((c.width + kWave * vec - 1) / (kWave * vec));
+        const uint64_t blocks64 = (static_cast<uint64_t>(so.nbags) * nslice + kRowsSumWaves - 1) / kRowsSumWaves;
+        HA_REQUIRE(blocks64 < (1ull << 31), "%s: batch too large", who);
+        const bool few = (so.offsets ? (n + so.nbags - 1) / so.nbags : so.bag) <= 8;
+        const dim3 grid(static_cast<unsigned>(blocks64)), block(kRowsSumWaves * kWave);
+#define HA_RSUM_CASE(V, R)                                                                                                   \
+    hipLaunchKernelGGL((cache_lookup_rows_sum_kernel<V, R>), grid, block, 0, s, c, p.uniq, p.inverse, p.seg, p.perm, (long long)n, \
+                       (long long)so.bag, so.offsets, (long long)so.nbags, nslice, so.out)
+        if (vec == 4) {
+            if (few) HA_RSUM_CASE(4, 8); else HA_RSUM_CASE(4, 32);
+        } else {
+            if (few) HA_RSUM_CASE(1, 8); else HA_RSUM_CASE(1, 32);
+        }
+#undef HA_RSUM_CASE
+    }
+    if (n > 0 && evb)
+        hipLaunchKernelGGL(cache_lookup_rows_kernel<1>, dim3(1), dim3(1024), 0, s, c, p.uniq, p.upos, p.perm, (long long)n,
+                           static_cast<float *>(nullptr), evb, c.bypass ? 1 : 0);
+    return 0;
+}
+
 // ---- remote store: inbox / outbox ------------------------------------------------------------------------
 // request of a lookup: (key, cached version) of every unique key -- what the reference's client hands to
 // syncEmbedding (hetu_client.cc:6-23: keys + the lines' versions)
@@ -2018,9 +2297,16 @@ extern "C" int ha_cache_lookup_begin(ha_cache *h, const void *keys, int key_kind
 }
 
 // second half: the inbox holds the owner's answer for the request of ha_cache_lookup_begin
-extern "C" int ha_cache_lookup_finish(ha_cache *h, int64_t n, float *dest, ha_stream_t stream) {
+static int cache_lookup_finish_impl(ha_cache *h, int64_t n, float *dest, const SumOut *sum, ha_stream_t stream) {
+    if (sum) {
+        HA_REQUIRE(h, "ha_cache_lookup_sum_finish: null handle");
+        if (sum_args_ok("ha_cache_lookup_sum_finish", n, *sum))
+            return -1;
+        HA_REQUIRE(h->c.remote, "ha_cache_lookup_sum_finish: the cache is not in remote-store mode");
+        HA_REQUIRE(h->plan_n == n, "ha_cache_lookup_sum_finish: no ha_cache_lookup_begin of %ld keys precedes", (long)n);
+    }
     HA_REQUIRE(h && h->c.remote, "cache_lookup_finish: the cache is not in remote-store mode");
-    HA_REQUIRE(h->plan_n == n && (n == 0 || dest), "cache_lookup_finish: no ha_cache_lookup_begin of %ld keys precedes",
+    HA_REQUIRE(h->plan_n == n && (n == 0 || dest || sum), "cache_lookup_finish: no ha_cache_lookup_begin of %ld keys precedes",
                (long)n);
     Cache c = h->c;
     c.data_row = c.inbox_pull;   // the decisions the bookkeeping and the row kernel read
@@ -2032,7 +2318,10 @@ extern "C" int ha_cache_lookup_finish(ha_cache *h, int64_t n, float *dest, ha_st
                        (long long)n, c.bypass ? 1 : 0, 1, evb);
     if (n > 0 && evb && c.policy != kLRU && c.S >= kScanWideFrom)      // LFU / LFUOpt: the victim scan of a large cache, in parallel
         hipLaunchKernelGGL(cache_scan_victim_part_kernel, dim3(kScanParts), dim3(1024), 0, s, c.ctl, c);
-    if (n > 0) {
+    if (sum) {
+        if (lookup_sum_rows(c, p, n, *sum, evb, s, "ha_cache_lookup_sum_finish"))
+            return -1;
+    } else if (n > 0) {
         const unsigned blocks = static_cast<unsigned>((n + 15) / 16) + (evb ? 1 : 0);
         const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(dest) % 16 == 0);
         if (vec_ok)
@@ -2045,6 +2334,18 @@ extern "C" int ha_cache_lookup_finish(ha_cache *h, int64_t n, float *dest, ha_st
     cache_mark(h, kTEnd, s);
     HA_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int ha_cache_lookup_finish(ha_cache *h, int64_t n, float *dest, ha_stream_t stream) {
+    return cache_lookup_finish_impl(h, n, dest, nullptr, stream);
+}
+
+// the same, delivered sum-pooled (cache_lookup_rows_sum_kernel): out[nbags, width]; the cache is left as ha_cache_lookup_finish
+// leaves it
+extern "C" int ha_cache_lookup_sum_finish(ha_cache *h, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
+                                          ha_stream_t stream) {
+    const SumOut so{nbags, bag, offsets, out};
+    return cache_lookup_finish_impl(h, n, nullptr, &so, stream);
 }
 
 // entries of the outbox the last ha_cache_update* left (synchronises the stream)
@@ -2147,7 +2448,7 @@ extern "C" int ha_cache_sort_ahead_batch(ha_cache *h, const void *const *keys, i
 }
 
 static int cache_lookup_impl(ha_cache *h, const void *keys, int key_kind, int64_t n, float *dest, hipStream_t s, bool presorted,
-                             bool from_ring = false);
+                             bool from_ring = false, const SumOut *sum = nullptr);
 
 extern "C" int ha_cache_lookup(ha_cache *h, const void *keys, int key_kind, int64_t n,
                                float *dest, ha_stream_t stream) {
@@ -2155,8 +2456,36 @@ extern "C" int ha_cache_lookup(ha_cache *h, const void *keys, int key_kind, int6
 }
 
 // The lookup of the keys ha_cache_sort_ahead was last given (same pointer, kind and count -- anything else is an error).
+static int cache_lookup_presorted_impl(ha_cache *h, const void *keys, int key_kind, int64_t n, float *dest, const SumOut *sum,
+                                       ha_stream_t stream);
 extern "C" int ha_cache_lookup_presorted(ha_cache *h, const void *keys, int key_kind, int64_t n,
                                          float *dest, ha_stream_t stream) {
+    return cache_lookup_presorted_impl(h, keys, key_kind, n, dest, nullptr, stream);
+}
+
+// The pooled forms of ha_cache_lookup / ha_cache_lookup_presorted: out[b,:] = the position-ordered sum over the rows of bag b's
+// keys (cache_lookup_rows_sum_kernel), bit for bit the unpooled lookup followed by ha_gather_sum over its rows; same ahead / ring
+// handling, same bookkeeping, same line state and perf counts.  Fixed bags: bag >= 1, offsets NULL, nbags * bag == n; ragged
+// bags: bag == 0, offsets int64[nbags + 1] (clamped to [0, n]).
+extern "C" int ha_cache_lookup_sum(ha_cache *h, const void *keys, int key_kind, int64_t n, int64_t nbags, int64_t bag,
+                                   const int64_t *offsets, float *out, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_lookup_sum: null handle");
+    const SumOut so{nbags, bag, offsets, out};
+    if (sum_args_ok("ha_cache_lookup_sum", n, so))
+        return -1;
+    return cache_lookup_impl(h, keys, key_kind, n, nullptr, as_stream(stream), false, false, &so);
+}
+extern "C" int ha_cache_lookup_sum_presorted(ha_cache *h, const void *keys, int key_kind, int64_t n, int64_t nbags, int64_t bag,
+                                             const int64_t *offsets, float *out, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_lookup_sum_presorted: null handle");
+    const SumOut so{nbags, bag, offsets, out};
+    if (sum_args_ok("ha_cache_lookup_sum_presorted", n, so))
+        return -1;
+    return cache_lookup_presorted_impl(h, keys, key_kind, n, nullptr, &so, stream);
+}
+
+static int cache_lookup_presorted_impl(ha_cache *h, const void *keys, int key_kind, int64_t n, float *dest, const SumOut *sum,
+                                       ha_stream_t stream) {
     HA_REQUIRE(h, "cache_lookup_presorted: null handle");
     if (h->ring_head < h->ring_count) {      // the next batch of ha_cache_sort_ahead_batch's ring
         const int i = h->ring_head;
@@ -2168,20 +2497,20 @@ extern "C" int ha_cache_lookup_presorted(ha_cache *h, const void *keys, int key_
         h->ring_ws[i] = h->c.plan_ws;        // (all workspaces are of one size: the ring keeps the lookup's old one)
         h->c.plan_ws = ws;
         ++h->ring_head;
-        return cache_lookup_impl(h, keys, key_kind, n, dest, as_stream(stream), true, true);
+        return cache_lookup_impl(h, keys, key_kind, n, dest, as_stream(stream), true, true, sum);
     }
     if (n == 0 || n > kSmallMax)      // sort_ahead ignored this batch
-        return cache_lookup_impl(h, keys, key_kind, n, dest, as_stream(stream), false);
+        return cache_lookup_impl(h, keys, key_kind, n, dest, as_stream(stream), false, false, sum);
     HA_REQUIRE(h->ahead_n == n && h->ahead_keys == keys && h->ahead_kind == key_kind,
                "cache_lookup_presorted: no ha_cache_sort_ahead of these %ld keys precedes", (long)n);
-    return cache_lookup_impl(h, keys, key_kind, n, dest, as_stream(stream), true);
+    return cache_lookup_impl(h, keys, key_kind, n, dest, as_stream(stream), true, false, sum);
 }
 
 static int cache_lookup_impl(ha_cache *h, const void *keys, int key_kind, int64_t n, float *dest, hipStream_t s,
-                             bool presorted, bool from_ring) {
+                             bool presorted, bool from_ring, const SumOut *sum) {
     HA_REQUIRE(h && h->c.table && !h->c.remote, "cache_lookup: no local store bound (remote stores use "
                "ha_cache_lookup_begin / ha_cache_lookup_finish)");
-    HA_REQUIRE(n >= 0 && (n == 0 || (keys && dest)), "cache_lookup: bad arguments");
+    HA_REQUIRE(n >= 0 && (n == 0 || (keys && (dest || sum))), "cache_lookup: bad arguments");
     HA_REQUIRE(ha_cache_plan_pending(h) == 0, "cache: %d planned calls are outstanding (ha_cache_plan_block): ha_cache_lookup_planned / "
                "ha_cache_update_planned come first", ha_cache_plan_pending(h));
     HA_CACHE_CHAIN_CLOSED(h, "cache_lookup");
@@ -2226,7 +2555,10 @@ static int cache_lookup_impl(ha_cache *h, const void *keys, int key_kind, int64_
     cache_mark(h, kTLookup, s);
     if (n > 0 && evb && c.policy != kLRU && c.S >= kScanWideFrom)      // LFU / LFUOpt: the victim scan of a large cache, in parallel
         hipLaunchKernelGGL(cache_scan_victim_part_kernel, dim3(kScanParts), dim3(1024), 0, s, c.ctl, c);
-    if (n > 0) {
+    if (sum) {
+        if (lookup_sum_rows(c, p, n, *sum, evb, s, "ha_cache_lookup_sum"))
+            return -1;
+    } else if (n > 0) {
         const unsigned blocks = static_cast<unsigned>((n + 15) / 16) + (evb ? 1 : 0);
         const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(dest) % 16 == 0) &&
                             (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
@@ -2247,7 +2579,9 @@ static int cache_lookup_impl(ha_cache *h, const void *keys, int key_kind, int64_
 static int cache_update_impl(ha_cache *h, const void *keys, int key_kind, int64_t n,
                              const float *grads, const void *push_keys, int push_kind,
                              int64_t n_push, int with_push_keys, hipStream_t s,
-                             bool defer_cleanup = false) {
+                             bool defer_cleanup = false, const BagSrc *bags = nullptr) {
+    // bags: `grads` is the POOLED gradient [nbags, width]; occurrence i reads its bag's row (ha_apply_mapped2_bags) -- the same
+    // values in the same order as the expanded [n, width] tensor, so the same bits on both paths below
     HA_REQUIRE(h && (h->c.table || h->c.remote), "cache_update: no store bound");
     HA_REQUIRE(n >= 0 && (n == 0 || grads), "cache_update: bad arguments");
     HA_REQUIRE(ha_cache_plan_pending(h) == 0, "cache: %d planned calls are outstanding (ha_cache_plan_block): ha_cache_lookup_planned / "
@@ -2275,7 +2609,9 @@ static int cache_update_impl(ha_cache *h, const void *keys, int key_kind, int64_
     if (fast) {
         ++h->fused_count;
         // every key is resident with data in uslot[]: accumulate, then touch / flags / push / commit in one launch
-        if (ha_apply_mapped2(c.grad, c.S, c.data, c.width, c.plan_ws, n, grads, -1.0f, c.uslot, c.uslot, c.hasgrad, s))
+        if (bags ? ha_apply_mapped2_bags(c.grad, c.S, c.data, c.width, c.plan_ws, n, grads, -1.0f, c.uslot, c.uslot, bags->bag,
+                                         bags->bag_of, c.hasgrad, s)
+                 : ha_apply_mapped2(c.grad, c.S, c.data, c.width, c.plan_ws, n, grads, -1.0f, c.uslot, c.uslot, c.hasgrad, s))
             return -1;
         cache_mark(h, kTCopy, s);
         const unsigned pblocks = static_cast<unsigned>((2 * n + 15) / 16 > 1024 ? 1024 : (2 * n + 15) / 16);
@@ -2310,8 +2646,10 @@ static int cache_update_impl(ha_cache *h, const void *keys, int key_kind, int64_
     // Line::accumulate per occurrence, occurrence order: grad += g (every line), data += g (lines
     // with data).  lr = -1 turns the SGD chain `acc - lr*g` into `acc + g` bit for bit.
     if (n > 0) {
-        if (ha_apply_mapped2(c.grad, c.S, c.data, c.width, c.plan_ws, n, grads, -1.0f, c.uslot, c.data_row,
-                             c.hasgrad, s))
+        if (bags ? ha_apply_mapped2_bags(c.grad, c.S, c.data, c.width, c.plan_ws, n, grads, -1.0f, c.uslot, c.data_row, bags->bag,
+                                         bags->bag_of, c.hasgrad, s)
+                 : ha_apply_mapped2(c.grad, c.S, c.data, c.width, c.plan_ws, n, grads, -1.0f, c.uslot, c.data_row,
+                                    c.hasgrad, s))
             return -1;
     }
     cache_mark(h, kTCopy, s);
@@ -2352,6 +2690,39 @@ extern "C" int ha_cache_update_with_push_keys(ha_cache *h, const void *keys, int
                              as_stream(stream));
 }
 
+// The updates from a POOLED gradient bag_grads[nbags, width] (fixed bags: bag >= 1, bag_of NULL, nbags * bag == n; ragged: bag ==
+// 0, bag_of int32[n]): the unpooled call on bag_grads expanded to [n, width], bit for bit, on the fused two-launch path and on
+// the general one, over local and remote stores.
+extern "C" int ha_cache_update_bags(ha_cache *h, const void *keys, int key_kind, int64_t n, const float *bag_grads,
+                                    int64_t nbags, int64_t bag, const int32_t *bag_of, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_update_bags: null handle");
+    const BagSrc bs{nbags, bag, bag_of};
+    if (bag_src_ok("ha_cache_update_bags", n, bag_grads, bs))
+        return -1;
+    HA_REQUIRE(n == 0 || keys, "ha_cache_update_bags: null keys");
+    return cache_update_impl(h, keys, key_kind, n, bag_grads, nullptr, 0, 0, 0, as_stream(stream), false, &bs);
+}
+
+extern "C" int ha_cache_update_same_keys_bags(ha_cache *h, int64_t n, const float *bag_grads, int64_t nbags, int64_t bag,
+                                              const int32_t *bag_of, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_update_same_keys_bags: null handle");
+    const BagSrc bs{nbags, bag, bag_of};
+    if (bag_src_ok("ha_cache_update_same_keys_bags", n, bag_grads, bs))
+        return -1;
+    return cache_update_impl(h, nullptr, 0, n, bag_grads, nullptr, 0, 0, 0, as_stream(stream), false, &bs);
+}
+
+extern "C" int ha_cache_update_with_push_keys_bags(ha_cache *h, const void *keys, int key_kind, int64_t n, const void *push_keys,
+                                                   int push_kind, int64_t n_push, const float *bag_grads, int64_t nbags,
+                                                   int64_t bag, const int32_t *bag_of, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_update_with_push_keys_bags: null handle");
+    const BagSrc bs{nbags, bag, bag_of};
+    if (bag_src_ok("ha_cache_update_with_push_keys_bags", n, bag_grads, bs))
+        return -1;
+    HA_REQUIRE((n == 0 || keys) && n_push >= 0 && (n_push == 0 || push_keys), "ha_cache_update_with_push_keys_bags: null keys");
+    return cache_update_impl(h, keys, key_kind, n, bag_grads, push_keys, push_kind, n_push, 1, as_stream(stream), false, &bs);
+}
+
 // embedding_push_pull (cache.cc:356-422): pull phase (touch + new lines) on scratch set B, push phase
 // (touch, accumulate, push incl. pending evictions) on scratch set A, then -- as
 // PSHandler::serve(kPushSyncEmbedding) pushes before it syncs (PSFhandle_embedding.cc:66-79) -- the
@@ -2371,7 +2742,7 @@ static Cache scratch_b_view(const Cache &c) {
 // and the request of the pull keys is exported.
 static int push_pull_begin(ha_cache *h, const void *pull_keys, int pull_kind, int64_t n_pull,
                            const void *push_keys, int push_kind, int64_t n_push, const float *grads,
-                           hipStream_t s) {
+                           hipStream_t s, const BagSrc *bags = nullptr) {
     HA_REQUIRE(n_pull >= 0 && n_push >= 0 && n_pull <= h->c.nmax && n_push <= h->c.nmax,
                "cache_push_pull: bad sizes");
     HA_REQUIRE((n_pull == 0 || pull_keys) && (n_push == 0 || (push_keys && grads)),
@@ -2402,7 +2773,7 @@ static int push_pull_begin(ha_cache *h, const void *pull_keys, int pull_kind, in
     hipLaunchKernelGGL(cache_retire_kernel, dim3(1), dim3(1), 0, s, c.ctl, 1);
     HA_LAUNCH_CHECK();
     // ---- push phase (a complete embedding_update on scratch set A)
-    if (cache_update_impl(h, push_keys, push_kind, n_push, grads, nullptr, 0, 0, 0, s, true))
+    if (cache_update_impl(h, push_keys, push_kind, n_push, grads, nullptr, 0, 0, 0, s, true, bags))
         return -1;
     h->evict_empty = false;    // the pull phase's insert evicts after this push
     // ---- pull phase, part 2 starts: restore the parked pull state
@@ -2415,13 +2786,22 @@ static int push_pull_begin(ha_cache *h, const void *pull_keys, int pull_kind, in
     return 0;
 }
 
-static int push_pull_finish(ha_cache *h, int64_t n_pull, float *dest, int64_t n_push, hipStream_t s) {
+// sum: the pull side delivered sum-pooled -- the per-occurrence slots (cache_slot_map_kernel) and the bag sum over the cache's data
+// rows (bag_sum_kernel, one chain in position order) in place of the copy to dest[n, width]
+static int push_pull_finish(ha_cache *h, int64_t n_pull, float *dest, int64_t n_push, hipStream_t s, const SumOut *sum = nullptr) {
     Cache &c = h->c;
     Cache cb = scratch_b_view(c);
     const dim3 b(256);
     PlanPtrs pp = plan_layout(cb.plan_ws, n_pull);
     hipLaunchKernelGGL(cache_sync_kernel, CACHE_GRID(n_pull * 64), b, 0, s, c.ctl, cb, pp.uniq);
-    if (n_pull > 0)
+    if (sum) {
+        if (n_pull > 0)
+            hipLaunchKernelGGL(cache_slot_map_kernel, CACHE_GRID(n_pull), b, 0, s, cb, pp.inverse, (long long)n_pull,
+                               c.pushkeys_u32);
+        HA_LAUNCH_CHECK();
+        if (ha_gather_sum_u32keys(c.data, c.S, c.width, c.pushkeys_u32, n_pull, sum->bag, sum->offsets, sum->nbags, sum->out, s))
+            return -1;
+    } else if (n_pull > 0)
         hipLaunchKernelGGL(cache_dest_kernel, CACHE_GRID(n_pull * c.width), b, 0, s, cb, pp.inverse,
                            (long long)n_pull, dest);
     if (c.policy != kLRU) {
@@ -2478,6 +2858,75 @@ extern "C" int ha_cache_push_pull_finish(ha_cache *h, float *dest, ha_stream_t s
     const int64_t n_pull = h->pp_pull, n_push = h->pp_push;
     h->pp_pull = -1;
     return push_pull_finish(h, n_pull, dest, n_push, as_stream(stream));
+}
+
+// embedding_push_pull with either side pooled (the two sides independently): the pull side delivers out[nbags_pull, width] (the
+// position-ordered sum over each bag of the pull keys' rows; nbags_pull < 0: unpooled, `out` is dest[n_pull, width]), the push
+// side takes bag_grads[nbags_push, width] (nbags_push < 0: unpooled, `bag_grads` is grads[n_push, width]).  Bit for bit
+// ha_cache_push_pull with ha_gather_sum over its rows and the expanded gradient; no [n, width] buffer on a pooled side.
+static int push_pull_bags_args(const char *who, ha_cache *h, int64_t n_pull, int64_t n_push, const float *bag_grads,
+                               const SumOut *so, const BagSrc *bs) {
+    if (so && sum_args_ok(who, n_pull, *so))
+        return -1;
+    if (bs && bag_src_ok(who, n_push, bag_grads, *bs))
+        return -1;
+    HA_REQUIRE(n_pull >= 0 && n_push >= 0 && n_pull <= h->c.nmax && n_push <= h->c.nmax, "%s: bad sizes", who);
+    return 0;
+}
+extern "C" int ha_cache_push_pull_bags(ha_cache *h, const void *pull_keys, int pull_kind, int64_t n_pull, int64_t nbags_pull,
+                                       int64_t bag_pull, const int64_t *pull_offsets, float *out, const void *push_keys,
+                                       int push_kind, int64_t n_push, const float *bag_grads, int64_t nbags_push,
+                                       int64_t bag_push, const int32_t *push_bag_of, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_push_pull_bags: null handle");
+    const SumOut so{nbags_pull, bag_pull, pull_offsets, out};
+    const BagSrc bs{nbags_push, bag_push, push_bag_of};
+    const SumOut *sop = nbags_pull >= 0 ? &so : nullptr;
+    const BagSrc *bsp = nbags_push >= 0 ? &bs : nullptr;
+    if (push_pull_bags_args("ha_cache_push_pull_bags", h, n_pull, n_push, bag_grads, sop, bsp))
+        return -1;
+    HA_REQUIRE(h->c.table && !h->c.remote, "ha_cache_push_pull_bags: needs a local store (over a remote store: "
+               "ha_cache_push_pull_begin_bags, the exchange, ha_cache_push_pull_finish_sum)");
+    HA_REQUIRE(sop || n_pull == 0 || out, "ha_cache_push_pull_bags: null dest");
+    hipStream_t s = as_stream(stream);
+    if (push_pull_begin(h, pull_keys, pull_kind, n_pull, push_keys, push_kind, n_push, bag_grads, s, bsp))
+        return -1;
+    return push_pull_finish(h, n_pull, out, n_push, s, sop);
+}
+
+// remote store: ha_cache_push_pull_begin with a pooled push side ...
+extern "C" int ha_cache_push_pull_begin_bags(ha_cache *h, const void *pull_keys, int pull_kind, int64_t n_pull,
+                                             const void *push_keys, int push_kind, int64_t n_push, const float *bag_grads,
+                                             int64_t nbags_push, int64_t bag_push, const int32_t *push_bag_of,
+                                             int64_t *n_unique_pull_host, ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_push_pull_begin_bags: null handle");
+    const BagSrc bs{nbags_push, bag_push, push_bag_of};
+    if (push_pull_bags_args("ha_cache_push_pull_begin_bags", h, n_pull, n_push, bag_grads, nullptr, &bs))
+        return -1;
+    HA_REQUIRE(h->c.remote, "ha_cache_push_pull_begin_bags: the cache is not in remote-store mode");
+    hipStream_t s = as_stream(stream);
+    if (push_pull_begin(h, pull_keys, pull_kind, n_pull, push_keys, push_kind, n_push, bag_grads, s, &bs))
+        return -1;
+    h->pp_pull = n_pull;
+    h->pp_push = n_push;
+    if (n_unique_pull_host) {
+        PlanPtrs pp = plan_layout(h->c.plan_ws_b, n_pull);
+        HA_CHECK_HIP(hipMemcpyAsync(n_unique_pull_host, &pp.hdr->n_unique, 8, hipMemcpyDeviceToHost, s));
+        HA_CHECK_HIP(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+// ... and ha_cache_push_pull_finish with a pooled pull side (after either begin)
+extern "C" int ha_cache_push_pull_finish_sum(ha_cache *h, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
+                                             ha_stream_t stream) {
+    HA_REQUIRE(h, "ha_cache_push_pull_finish_sum: null handle");
+    HA_REQUIRE(h->c.remote && h->pp_pull >= 0, "ha_cache_push_pull_finish_sum: no ha_cache_push_pull_begin precedes");
+    const SumOut so{nbags, bag, offsets, out};
+    if (sum_args_ok("ha_cache_push_pull_finish_sum", h->pp_pull, so))
+        return -1;
+    const int64_t n_pull = h->pp_pull, n_push = h->pp_push;
+    h->pp_pull = -1;
+    return push_pull_finish(h, n_pull, nullptr, n_push, as_stream(stream), &so);
 }
 
 // out[8]: last op report {type, num_all, num_unique, num_miss, num_transfered, num_evict, is_full, size}

@@ -12,9 +12,9 @@ Mirrors (paths relative to /root/reference):
                                                   straight from the pooled gradient of EmbeddingLookUpSum_Gradient)
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
-cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and three switches of this build: cache_plan_ahead (the cache's
+cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and four switches of this build: cache_plan_ahead (the cache's
 planned flow), cache_fuse_bags (with it, at bsp 0 and on the LRU asp chain: a sum-pooled lookup is pulled and pushed pooled, see
-Config) and
+Config), cache_fuse_bag_calls (the same through the cache's call-by-call interface, off by default) and
 ps_fuse_bags (the same on the plain PS flavour, every schedule).  The data loader contract is the reference's
 `get_arr` / `get_next_arr` (python/hetu/dataloader.py:63-98): `next_ids()` returns the ids of the batch
 after the current one.  Everything computed goes through libherald_amd.so.
@@ -31,7 +31,7 @@ from .sharded import ShardedEmbedding
 class Config:
     def __init__(self, comm_mode=None, bsp=0, prefetch=True, cstable_policy=None, cache_bound=100, cache_limit=0,
                  use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False, cache_fuse_bags=True,
-                 ps_fuse_bags=True):
+                 ps_fuse_bags=True, cache_fuse_bag_calls=False):
         self.comm_mode, self.bsp, self.prefetch = comm_mode, bsp, prefetch
         # not a HetuConfig field: the cache's PLANNED flow (csrc/cache_block.hip) for the bsp-prefetch schedule -- the bookkeeping
         # of batch k + 1 runs on a side stream beside the model's step on batch k.  Needs ids one batch further ahead than
@@ -46,6 +46,12 @@ class Config:
         # path (per-occurrence rows, a summing pass, the expanded gradient).  Every other schedule -- ssp, no prefetch,
         # world > 1, the call-by-call cache (LFU / LFUOpt at bsp < 0 included), laia push plans in a chain -- is unfused.
         self.cache_fuse_bags = cache_fuse_bags
+        # the same for the prefetching schedules whose cache flow is CALL BY CALL -- no cache_plan_ahead, LFU / LFUOpt at bsp < 0,
+        # the cache over a sharded store (world > 1), laia (ids, push plan) tuples: a communicate op that was told its bag size
+        # pulls with embedding_lookup_sum, pushes with embedding_update_bags / embedding_update_with_push_keys_bags and, on the
+        # asp schedule, makes embedding_push_pull_bags; sparse_pull_val is [B, width], the same bits.  Off by default: the
+        # unfused shapes of those flows are what existing callers see.
+        self.cache_fuse_bag_calls = cache_fuse_bag_calls
         # the same switch for the plain PS flavour (no cstable_policy; ssp, asp and no prefetch alike): a communicate op that
         # was told its bag size pulls pooled rows (ShardedEmbedding.pull_sum) and pushes the pooled gradient (push_bags), and
         # without prefetch EmbeddingLookUpSum pulls pooled rows itself (ragged bags too) -- that lookup reads this switch alone:
@@ -149,8 +155,8 @@ class EmbeddingLookUpSum(EmbeddingLookUp):
     (Config.ps_fuse_bags) -- with prefetch the communicate op's buffer already holds the pooled rows (the cache, or the
     sharded store's pull_sum, summed them as it read them) and is copied as it is; without prefetch the rows come from
     store.pull_sum directly, ragged bags included, whether or not the communicate op was told a bag size (`stream` is not
-    used there: the store works on the current stream, as its pull does).  The call-by-call cache and ps_fuse_bags=False still
-    move [n, width] rows."""
+    used there: the store works on the current stream, as its pull does).  The call-by-call cache with prefetch is fused under
+    Config.cache_fuse_bag_calls (off by default); without it, and with ps_fuse_bags=False, [n, width] rows still move."""
 
     def forward_hook(self, config):
         super().forward_hook(config)
@@ -334,8 +340,9 @@ class ParameterServerCommunicateOp:
         bag (optional): the embedding is read through a sum-pooled lookup (EmbeddingLookUpSum) with fixed bags of `bag` ids --
         ids arrive as [B, bag].  With the cache's planned flow (the pairs at bsp 0, the LRU push-pull chain of the asp schedule)
         and Config.cache_fuse_bags, or on the plain PS flavour with Config.ps_fuse_bags, the op then keeps sparse_pull_val as
-        [B, width] and moves pooled rows and pooled gradients only; on every other path (the call-by-call cache, a chain with
-        laia push plans, the cache over a sharded store) it changes nothing.
+        [B, width] and moves pooled rows and pooled gradients only; so it does on the call-by-call cache flows (no plan-ahead,
+        LFU / LFUOpt at bsp < 0, the cache over a sharded store, laia push plans) with Config.cache_fuse_bag_calls; on every
+        other path it changes nothing.
         Without bag= the op's pulls and pushes are per occurrence as they always were; the lookup without prefetch
         (EmbeddingLookUpSum -> store.pull_sum) does not pass through this op and follows Config.ps_fuse_bags alone."""
         self.parameter = parameter
@@ -348,6 +355,7 @@ class ParameterServerCommunicateOp:
         self._ps_bags = False         # ... by the plain PS flavour (store.pull_sum / push_bags)
         self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
         self._chain = False           # the planned flow of the asp schedule: _planned = ids of a push-pull chain's batches
+        self._bag_calls = False       # pooled rows through the call-by-call cache (Config.cache_fuse_bag_calls)
 
     def forward_hook(self, config, first_ids=None, barrier=lambda: None):   # :130-242
         self.config, self.barrier = config, barrier
@@ -399,6 +407,9 @@ class ParameterServerCommunicateOp:
                         self._bag = self.bag      # ... with pooled entries: embedding_push_pull_planned_bags
             else:
                 self.compute = self._compute_no_prefetch
+            if config.prefetch and self._planned is None and self.bag is not None and \
+                    getattr(config, "cache_fuse_bag_calls", False):
+                self._bag, self._bag_calls = self.bag, True       # the call-by-call flow, pooled
         else:
             self._push, self._pull, self._push_pull = self._push_sparse, self._pull_sparse, self._push_pull_sparse
             if self.bag is not None and getattr(config, "ps_fuse_bags", True):
@@ -434,9 +445,10 @@ class ParameterServerCommunicateOp:
     # -- compute variants (:37-56)
     def _per_occurrence(self, grad):
         """Pooled slices (the gradient of EmbeddingLookUpSum: one row per bag) are expanded to per-occurrence values before
-        they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The call-by-call
-        cache and the step engines are NOT fused for pooled access: they move the expanded [n, width] values as they always
-        did.  The cache's planned flow -- pairs and the asp chain -- (Config.cache_fuse_bags) and the plain PS flavour
+        they are pushed -- what reduce_sum_op's broadcast gradient hands the reference's communicate op.  The step engines are
+        NOT fused for pooled access, and the call-by-call cache is only with Config.cache_fuse_bag_calls (off by default):
+        otherwise they move the expanded [n, width] values as they always did.  The cache's planned flow -- pairs and the asp
+        chain -- (Config.cache_fuse_bags), the call-by-call cache under its switch and the plain PS flavour
         (Config.ps_fuse_bags) are: slices
         pooled by the op's own bag size stay [B, width] -- on the PS flavour ragged slices that carry their offsets too --;
         -lr is applied to those rows only, which is the same product for every occurrence of a bag."""
@@ -488,8 +500,23 @@ class ParameterServerCommunicateOp:
             w.wait()
 
     # -- cache flavour (:68-72, 88-92, 104-105)
+    def _pooled_by_bag(self, grad):
+        """Call-by-call pooled flow: the pull buffer holds pooled rows, so the gradients are the pooled slices of this bag size."""
+        if not (getattr(grad, "pooled", False) and grad.bag == self._bag):
+            raise RuntimeError("ParameterServerCommunicateOp (cache_fuse_bag_calls, bag=%d): the pull buffer holds pooled rows, "
+                               "so the gradients must be the pooled slices of EmbeddingLookUpSum_Gradient over bags of %d ids; "
+                               "use cache_fuse_bag_calls=False for per-occurrence gradients" % (self._bag, self._bag))
+
     def _push_cache(self, grad):
         vals = grad.values.reshape(-1, self.parameter.shape[1])
+        if self._bag_calls:
+            self._pooled_by_bag(grad)
+            idx = grad.indices.reshape(-1)
+            if grad.push_indices is None:
+                return self.cache.embedding_update_bags(idx, vals.contiguous(), bag=self._bag,
+                                                        same_as_lookup=self.cache.looked_up_last(idx))
+            return self.cache.embedding_update_with_push_keys_bags(idx, grad.push_indices.reshape(-1), vals.contiguous(),
+                                                                   bag=self._bag)
         if self._planned is not None:
             idx = grad.indices.reshape(-1)
             pk = grad.push_indices.reshape(-1) if grad.push_indices is not None else None
@@ -553,6 +580,8 @@ class ParameterServerCommunicateOp:
             return self.cache.embedding_lookup_planned(dest)      # (no next batch: the next pull plans for itself)
         if isinstance(ids, tuple):              # (ids, push plan) of a laia-scheduled batch (cstable.py:49)
             ids = ids[0]
+        if self._bag_calls:                     # dest is [B, width]
+            return self.cache.embedding_lookup_sum(ids.reshape(-1), dest, bag=self._bag)
         return self.cache.embedding_lookup(ids.reshape(-1), dest)
 
     def _plan_chain(self, ids):
@@ -596,6 +625,13 @@ class ParameterServerCommunicateOp:
     def _push_pull_cache(self, grad):
         if self._chain:
             return self._push_pull_planned(grad)
+        if self._bag_calls:
+            self._pooled_by_bag(grad)
+            nxt = self.next_ids()
+            width = self.parameter.shape[1]
+            return self.cache.embedding_push_pull_bags((nxt[0] if isinstance(nxt, tuple) else nxt).reshape(-1),
+                                                       self.sparse_pull_val.reshape(-1, width), grad.indices.reshape(-1),
+                                                       grad.values.reshape(-1, width).contiguous(), bag=self._bag)
         nxt = self.next_ids()
         return self.cache.embedding_push_pull((nxt[0] if isinstance(nxt, tuple) else nxt).reshape(-1),
                                               self.sparse_pull_val.reshape(-1, self.parameter.shape[1]),

@@ -356,6 +356,12 @@ int ha_apply_mapped2(float *dst, int64_t dst_rows, float *dst2, int64_t width,
                      const void *plan_ws, int64_t n, const float *src, float lr,
                      const int32_t *rowmap, const int32_t *rowmap2,
                      const uint8_t *dst_init, ha_stream_t stream);
+/* ha_apply_mapped2 with src = bag_grads[nbags, width] expanded to [n, width], without the expanded tensor: occurrence i reads
+ * row i / bag (fixed bags: bag >= 1, bag_of NULL, n % bag == 0) or row bag_of[i] (ragged: bag == 0, device int32 bag_of[n]).
+ * Both destinations equal the unpooled call's bit for bit. */
+int ha_apply_mapped2_bags(float *dst, int64_t dst_rows, float *dst2, int64_t width, const void *plan_ws, int64_t n,
+                          const float *bag_grads, float lr, const int32_t *rowmap, const int32_t *rowmap2, int64_t bag,
+                          const int32_t *bag_of, const uint8_t *dst_init, ha_stream_t stream);
 
 /* ---- fused deduplicate + optimizer step -----------------------------------------------------------
  * One call for what the reference does in two (python/hetu/gpu_links/OptimizerLink.py:52-100:
@@ -1175,6 +1181,46 @@ int ha_cache_push_pull_begin(ha_cache *cache, const void *pull_keys, int pull_ki
                              const void *push_keys, int push_kind, int64_t n_push,
                              const float *grads, int64_t *n_unique_pull_host, ha_stream_t stream);
 int ha_cache_push_pull_finish(ha_cache *cache, float *dest, ha_stream_t stream);
+/* ---- sum-pooled access, call by call ("bags": embedding_lookup_op + reduce_sum_op(axes=1) of the emb_sum_* models) ----------
+ * The pooled twins of the call-by-call entry points above, for the callers the planned flow does not reach (a cache over a
+ * remote store, LFU / LFUOpt on the asp schedule, no ids a block ahead, push plans).  Bags as everywhere: fixed -- bag >= 1,
+ * the ragged description NULL, nbags * bag == n --, or ragged -- bag == 0 and device int64 offsets[nbags + 1] (a pull side;
+ * clamped to [0, n], an empty bag gives zeros) or device int32 bag_of[n] (a push side; ha_bag_of).  Every argument is checked
+ * before any device access and before anything is enqueued; a refused call changes nothing.
+ * Lookups: out[b,:] = ((0.0f + r_lo) + r_lo+1) + ... over the rows the unpooled call delivers for bag b's keys, in position
+ * order, one rounding per add -- bit for bit that call followed by ha_gather_sum over its rows; the [n, width] rows are never
+ * written.  Bookkeeping, line state, versions and ha_cache_perf counts are the unpooled call's; so is the handling of
+ * ha_cache_sort_ahead / ha_cache_sort_ahead_batch, and an ha_cache_update_same_keys* may follow either form.
+ * Updates: bag_grads[nbags, width] in place of grads[n, width]; occurrence i reads the row of its bag -- bit for bit the
+ * unpooled call on the expanded gradient, on the two-launch path (ha_cache_fused_updates counts it) and the general one. */
+int ha_cache_lookup_sum(ha_cache *cache, const void *keys, int key_kind, int64_t n, int64_t nbags, int64_t bag,
+                        const int64_t *offsets, float *out, ha_stream_t stream);
+int ha_cache_lookup_sum_presorted(ha_cache *cache, const void *keys, int key_kind, int64_t n, int64_t nbags, int64_t bag,
+                                  const int64_t *offsets, float *out, ha_stream_t stream);
+/* remote mode: the second half of a lookup, after the unchanged ha_cache_lookup_begin and the exchange */
+int ha_cache_lookup_sum_finish(ha_cache *cache, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
+                               ha_stream_t stream);
+int ha_cache_update_bags(ha_cache *cache, const void *keys, int key_kind, int64_t n, const float *bag_grads, int64_t nbags,
+                         int64_t bag, const int32_t *bag_of, ha_stream_t stream);
+int ha_cache_update_same_keys_bags(ha_cache *cache, int64_t n, const float *bag_grads, int64_t nbags, int64_t bag,
+                                   const int32_t *bag_of, ha_stream_t stream);
+int ha_cache_update_with_push_keys_bags(ha_cache *cache, const void *keys, int key_kind, int64_t n, const void *push_keys,
+                                        int push_kind, int64_t n_push, const float *bag_grads, int64_t nbags, int64_t bag,
+                                        const int32_t *bag_of, ha_stream_t stream);
+/* ha_cache_push_pull with its two sides pooled independently: the pull side delivers out[nbags_pull, width]; the push side takes
+ * bag_grads[nbags_push, width].  A side with nbags < 0 is NOT pooled: `out` is then dest[n_pull, width], `bag_grads` is
+ * grads[n_push, width], and the side's bag / ragged arguments are ignored.  Remote stores: ha_cache_push_pull_begin_bags (pooled
+ * push side) or ha_cache_push_pull_begin, the exchange, then ha_cache_push_pull_finish_sum (pooled pull side) or
+ * ha_cache_push_pull_finish. */
+int ha_cache_push_pull_bags(ha_cache *cache, const void *pull_keys, int pull_kind, int64_t n_pull, int64_t nbags_pull,
+                            int64_t bag_pull, const int64_t *pull_offsets, float *out, const void *push_keys, int push_kind,
+                            int64_t n_push, const float *bag_grads, int64_t nbags_push, int64_t bag_push,
+                            const int32_t *push_bag_of, ha_stream_t stream);
+int ha_cache_push_pull_begin_bags(ha_cache *cache, const void *pull_keys, int pull_kind, int64_t n_pull, const void *push_keys,
+                                  int push_kind, int64_t n_push, const float *bag_grads, int64_t nbags_push, int64_t bag_push,
+                                  const int32_t *push_bag_of, int64_t *n_unique_pull_host, ha_stream_t stream);
+int ha_cache_push_pull_finish_sum(ha_cache *cache, int64_t nbags, int64_t bag, const int64_t *offsets, float *out,
+                                  ha_stream_t stream);
 /* Owner side of a remote lookup (kSyncEmbedding, PSFhandle_embedding.cc:30-64) for m requested shard-local
  * keys: pull[j] = versions[j] == -1 || server_versions[key] - versions[j] > bound; pulled rows are packed
  * in request order into rows_out, idx[j] = its row there, ver_out[j] = the server version; *count_dev
