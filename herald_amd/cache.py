@@ -462,7 +462,7 @@ class _CacheBase:
                   "ha_cache_sort_ahead_batch")
 
     # ---- the planned flow: the bookkeeping of a block of batches ahead, ONE launch per lookup / update ----------------------
-    def plan_block(self, keys_list, side=None, push_keys_list=None, push_pull=False):
+    def plan_block(self, keys_list, side=None, push_keys_list=None, push_pull=False, after_current=False):
         """State that the device tensors of `keys_list` (1..16, one dtype, at most min(max_batch, 36,864) keys each) are the
         batches of the NEXT embedding_lookup_planned / embedding_update_planned pairs, in this order (ha_cache_plan_block,
         csrc/cache_block.hip: a local store; LRU: limit >= the batch; LFU / LFUOpt: every resident line updated since its lookup, as
@@ -483,7 +483,18 @@ class _CacheBase:
         The chain's first step has nothing to push and is made by embedding_lookup_planned; a None entry, allowed as the last
         one, closes the chain: its step is embedding_update_planned with the gradients of the batch pulled last; every other
         step is embedding_push_pull_planned(dest, grads).  Every step needs n_pull + n_push <= limit.  While a chain is open the
-        call-by-call methods and pair blocks raise; push_keys_list must be None."""
+        call-by-call methods and pair blocks raise; push_keys_list must be None.
+
+        WHO ORDERS THE IDS.  The key tensors are read on `side`.  With push_keys_list or push_pull=True that work is always
+        ordered behind everything enqueued on the cache's stream so far: ids and push keys written there just before the call
+        (an upload, `ids % rows`, a loader's gather) are read as written.  A plain block of pairs is NOT, from the fourth
+        block on: in steady state its bookkeeping waits only for the rows of the block that used its buffers three blocks
+        ago (no event wait parked on the planning stream's queue), so the key tensors must be complete on the device by other
+        means -- staged and synchronised ahead, as the benchmark and the tools do.  after_current=True (pair blocks; the other
+        two forms do it anyway) orders the planning stream behind the cache's stream at the time of the call, by an event
+        record and wait in front of ha_cache_plan_block: for callers that cannot know where a key tensor came from
+        (hetu_ops.ParameterServerCommunicateOp plans a loader's tensors this way).  What that extra wait costs per planned
+        block has not been measured."""
         if self._remote is not None or not keys_list:
             raise ValueError("plan_block: a non-empty list of key tensors, local store")
         closes = False
@@ -585,6 +596,14 @@ class _CacheBase:
         self._drop_ahead_ring()
         self._last_lookup = None
         if pks is None:
+            if after_current and side.cuda_stream != s.cuda_stream:
+                # (in front of the call, whose ABI takes no event: should the library refuse the block -- every argument check
+                # Python can make has passed by now -- the planning stream keeps one wait for work that is already queued)
+                ev = getattr(self, "_plan_after_ev", None)
+                if ev is None:
+                    ev = self._plan_after_ev = torch.cuda.Event()
+                ev.record(s)
+                side.wait_event(ev)
             check(self._L.ha_cache_plan_block(self._h, ptrs, kinds.pop(), ns, len(ks), ctypes.c_void_p(side.cuda_stream),
                                               ctypes.c_void_p(s.cuda_stream)), "ha_cache_plan_block")
         else:
@@ -1332,8 +1351,11 @@ class CacheSparseTable:
 
     # the planned flow (csrc/cache_block.hip): the ids of a block of batches a block early -- bookkeeping ahead on a side stream,
     # ONE launch per lookup and per update
-    def plan_block(self, keys_list, side=None, push_keys_list=None, push_pull=False):
-        self.cache.plan_block([k[0] if isinstance(k, tuple) else k for k in keys_list], side, push_keys_list, push_pull)
+    def plan_block(self, keys_list, side=None, push_keys_list=None, push_pull=False, after_current=False):
+        """after_current=True: the key tensors may have been written on the cache's stream just before the call (pair blocks
+        in steady state are otherwise not ordered behind it; see _CacheBase.plan_block)."""
+        self.cache.plan_block([k[0] if isinstance(k, tuple) else k for k in keys_list], side, push_keys_list, push_pull,
+                              after_current=after_current)
 
     def embedding_push_pull_planned(self, dest, grads, sync=False):
         w = self.cache.embedding_push_pull_planned(dest, grads)

@@ -1767,8 +1767,9 @@ extern "C" int ha_cache_plan_pending(ha_cache *h) {
 
 // The bookkeeping of the next `count` (1..16) batches: their lookups and updates follow as ha_cache_lookup_planned /
 // ha_cache_update_planned, in this order, lookup and update alternating.  `side`: the stream the plans and the bookkeeping
-// launch run on; `main`: the stream of the row launches (everything enqueued on it so far is ordered in front of the
-// bookkeeping: the row launches of the block that used this block's buffers before, or call-by-call entry points).  At most TWO
+// launch run on; `main`: the stream of the row launches (the row launches of the block that used this block's buffers before are
+// ordered in front of the bookkeeping; EVERYTHING enqueued on it so far only with push keys, for the first blocks and after
+// call-by-call entry points -- in steady state a bound-mode block's key buffers must be complete by other means).  At most TWO
 // blocks are outstanding (the one being consumed and the next).  The key buffers must stay unchanged until the bookkeeping
 // has run (event `booked`; the row launches wait for it).
 // push_keys == nullptr: every batch in bound mode (ha_cache_plan_block); else ha_cache_plan_block_push_keys (see the header).

@@ -538,13 +538,15 @@ class ParameterServerCommunicateOp:
 
     def _plan(self, batch):
         """Plan one batch: ids alone (the bounded push), or (ids, push plan) of a laia-scheduled batch (its update pushes the
-        plan's keys, cache.cc:248-335)."""
+        plan's keys, cache.cc:248-335).  The op cannot know where a loader's tensor came from (an upload or `ids % rows` on the
+        current stream): a pair block is planned with after_current=True, so the planning stream reads the ids behind
+        everything queued on the cache's stream (one event record and wait per planned batch; its cost is not measured)."""
         if isinstance(batch, tuple):
             ids, plan = batch[0].reshape(-1), batch[1].reshape(-1)
             self.cache.plan_block([ids], push_keys_list=[plan])
         else:
             ids, plan = batch.reshape(-1), None
-            self.cache.plan_block([ids])
+            self.cache.plan_block([ids], after_current=True)
         self._planned.append((ids, plan))
 
     def _pull_cache(self, ids):

@@ -1512,6 +1512,10 @@ class FramedStep:
                           lambda: self._push(k, v, scale, lay))
         self._pending = False
         self.k = k + 1
+        if self.k % self.block == 0:
+            # a block that ended step by step: the block-end event of the last NATIVE block is stale (batches were staged
+            # after it), so the next native block routes its successor behind everything queued on the step stream
+            self._ev_block_end = None
 
     # -- sum-pooled access (embedding_lookup_op + reduce_sum_op(axes=1) of the reference's emb_sum_* models) -----------------
     # Routing, owner gather, exchanges, owner merge and `stats` are those of pull / push -- the same rows cross the fabric --;
@@ -1665,6 +1669,7 @@ class FramedStep:
             self._route_block(route_after[0])        # (the fallback pulls and pushes step by step: the routing in its old place)
             route_after = None
         if not native:
+            self._ev_block_end = None          # (as in _push_step: whatever routes next must not wait for a stale event)
             res = []
             for i in range(cnt):
                 if lays is None:

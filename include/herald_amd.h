@@ -989,7 +989,9 @@ int ha_cache_sort_ahead_batch(ha_cache *cache, const void *const *keys, int key_
  * by the bookkeeping; they require that every resident line was updated since its lookup when the planned flow takes over --
  * true after any lookup + update pair), update counters and the bounded push (cache.cc:159) follow from the ids alone.  ha_cache_plan_block enqueues, on `side`, the index plans of the
  * block's batches and ONE bookkeeping launch that leaves per batch the items of its two row launches; `main` = the stream of
- * those row launches (what is enqueued on it so far is ordered in front of the bookkeeping).  Then, per batch and in order,
+ * those row launches (what is enqueued on it so far is ordered in front of the bookkeeping for the first blocks and after
+ * call-by-call calls ONLY: in steady state the key buffers must be complete on the device before the call -- see "Ordering"
+ * under ha_cache_plan_block_push_keys).  Then, per batch and in order,
  * ha_cache_lookup_planned (ONE launch: the staleness-bounded pull decided as the rows are read, rows to dest) and
  * ha_cache_update_planned (ONE launch: ordered accumulate, the pushed lines' store rows in the same pass, evicted dirty lines,
  * versions).  Results: those of ha_cache_lookup + ha_cache_update_same_keys call by call.  At most two blocks are outstanding
@@ -1012,8 +1014,10 @@ int ha_cache_plan_block(ha_cache *cache, const void *const *keys, int key_kind, 
  * ha_cache_lookup + ha_cache_update_with_push_keys call by call.
  * Ordering: this entry point ALWAYS orders its work on `side` behind everything enqueued on `main` so far (ids and push keys
  * written there just before the call are read as written).  ha_cache_plan_block does so only for the first blocks and after
- * call-by-call calls; in steady state it waits only for the rows of the block that last used its buffers, so key buffers it is
- * given must be complete by other means. */
+ * call-by-call calls; in steady state (from the fourth block on) it waits only for the rows of the block that last used its
+ * buffers, so key buffers it is given must be complete by other means: staged and synchronised ahead, or the caller makes
+ * `side` wait for an event it records on `main` in front of the call (herald_amd/cache.py: plan_block(after_current=True);
+ * the cost of that wait per block is not measured). */
 int ha_cache_plan_block_push_keys(ha_cache *cache, const void *const *keys, int key_kind, const int64_t *n,
                                   const void *const *push_keys, int push_kind, const int64_t *n_push, int count,
                                   ha_stream_t side, ha_stream_t main);
