@@ -47,6 +47,11 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      with the reference's default hyper-parameters (python/hetu/optimizer.py:232-483); the states live beside
                      the table.  A pooled model's gradient goes to the optimizer pooled as well (ha_sparse_opt_fused_bags_*,
                      ha_momentum_sparse_update_bags_*).  The dense tower keeps SGD.  Every other engine runs sparse SGD only.
+  --model deepfm     DeepFM (examples/ctr/models/deepfm_criteo.py): a first-order table [rows, 1] read through the sum-pooled
+                     lookup at width 1 and updated by the bag apply, and a second-order table [rows, d] whose one lookup feeds
+                     the DNN (rows), the sum S and the sum of squares Q -- the fused FM-pooled lookup (ha_gather_fm_*) writes
+                     rows, S and 0.5 * (S*S - Q) in one pass, ha_fm_grad_rows combines the gradients of the rows and of the FM
+                     output into one per-occurrence gradient for the ordinary sparse SGD.  --embedding hbm, --optimizer sgd.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -127,12 +132,59 @@ class SumTower(Tower):
         self.W4 = torch.nn.Parameter(torch.randn(256 + width, 1, generator=g) * 0.01)
 
 
+class FMTower(torch.nn.Module):
+    """The dense part of deepfm_criteo (models/deepfm_criteo.py:13-52): FM_W [13, 1] for the first-order dense part and the DNN
+    26d-256-256-1 over the flattened second-order rows; every weight ~ N(0, 0.01).  forward(dense, emb_flat [B, 26 d],
+    first [B, 1] = the sum of a sample's first-order weights, fm [B, d] = 0.5 * (S*S - Q)):
+    y = sigmoid(y1 + y2 + y3) with y1 = dense @ FM_W + first, y2 = fm.sum(1, keepdim) and y3 the DNN's output."""
+
+    def __init__(self, width, seed=0):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+
+        def w(*shape):
+            return torch.nn.Parameter(torch.randn(*shape, generator=g) * 0.01)
+        self.FM_W = w(NDENSE, 1)
+        self.W1, self.W2, self.W3 = w(NFIELD * width, 256), w(256, 256), w(256, 1)
+
+    def forward(self, dense, emb_flat, first, fm):
+        y1 = dense @ self.FM_W + first
+        y2 = fm.sum(1, keepdim=True)
+        y3 = torch.relu(torch.relu(emb_flat @ self.W1) @ self.W2) @ self.W3
+        return torch.sigmoid((y1 + y2) + y3)
+
+
+class FMLookup(torch.autograd.Function):
+    """EmbeddingLookUpFM and EmbeddingLookUpFM_Gradient as one autograd node: forward returns the rows [B, 26, d] and the FM
+    output [B, d] of one fused lookup; backward hands the gradients of both to the gradient operator, which combines them with
+    the forward's rows and sum into the per-occurrence gradient (in place over the rows' gradient) and leaves the
+    IndexedSlices in `sink`.  `anchor` is a scalar that requires grad: the table is no autograd leaf, the node needs one."""
+
+    @staticmethod
+    def forward(ctx, anchor, ids, lookup, lookup_grad, sink):
+        batch, width = ids.shape[0], lookup.embedding.shape[1]
+        rows = torch.empty((batch, NFIELD, width), dtype=torch.float32, device=ids.device)
+        total = torch.empty((batch, width), dtype=torch.float32, device=ids.device)
+        fm = torch.empty((batch, width), dtype=torch.float32, device=ids.device)
+        lookup.compute(ids, rows, total, fm)
+        ctx.save_for_backward(ids, rows, total)
+        ctx.lookup_grad, ctx.sink = lookup_grad, sink
+        return rows, fm
+
+    @staticmethod
+    def backward(ctx, g_rows, g_fm):
+        ids, rows, total = ctx.saved_tensors
+        ctx.sink["grad"] = ctx.lookup_grad.compute(g_rows.contiguous(), g_fm.contiguous(), rows, total, ids)
+        return None, None, None, None, None
+
+
 POOLED_MODELS = ("emb_sum_wdl",)
+FM_MODELS = ("deepfm",)
 OPTIMIZERS = ("sgd", "momentum", "nesterov", "adagrad", "adam", "adamw")
 
 
 def make_tower(model, width, seed=0):
-    return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower}[model](width, seed)
+    return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower, "deepfm": FMTower}[model](width, seed)
 
 
 def make_samples(nsamples, rows, seed=0):
@@ -247,10 +299,58 @@ def make_batches(nbatch, batch, rows, seed=0, rank=0, world=1):
     return out
 
 
+def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every):
+    """--model deepfm with both tables in HBM: the first-order table [rows, 1] through EmbeddingLookUpSum and the pooled SGD
+    apply, the second-order table [rows, width] through the FM operator pair (FMLookup) and the unpooled sparse SGD.  Returns
+    (losses, second-order parameter, tower); the first-order parameter is `parameter.first_order`."""
+    dev = torch.device(device)
+    tower = make_tower("deepfm", width, seed).to(dev)
+    opt = torch.optim.SGD(tower.parameters(), lr=lr)
+    dev_batches = [tuple(torch.from_numpy(a).to(dev) for a in b) for b in make_batches(min(steps + 1, 64), batch, rows, seed)]
+    if table_init is None:
+        g = torch.Generator(device=dev).manual_seed(seed + 1)
+        table_init = torch.randn((rows, width), generator=g, device=dev) * 0.01    # init.random_normal(stddev=0.01)
+    if first_order_init is None:
+        g = torch.Generator(device=dev).manual_seed(seed + 2)
+        first_order_init = torch.randn((rows, 1), generator=g, device=dev) * 0.01
+    config = hetu_ops.Config(comm_mode=None)
+    param = hetu_ops.EmbeddingParameter(table=table_init.clone())
+    param.first_order = first = hetu_ops.EmbeddingParameter(table=first_order_init.clone())
+    first_lookup = hetu_ops.EmbeddingLookUpSum(first)
+    first_lookup.forward_hook(config)
+    first_grad = hetu_ops.EmbeddingLookUpSum_Gradient(first.shape)
+    lookup = hetu_ops.EmbeddingLookUpFM(param)
+    lookup.forward_hook(config)
+    lookup_grad = hetu_ops.EmbeddingLookUpFM_Gradient(param.shape)
+    anchor = torch.zeros((), device=dev, requires_grad=True)
+    sink = {}
+    losses = []
+    t0 = time.perf_counter()
+    for k in range(steps):
+        ids, dense, label = dev_batches[k % len(dev_batches)]
+        y_first = torch.empty((batch, 1), dtype=torch.float32, device=dev)
+        first_lookup.compute(ids, y_first)                         # embedding_lookup_op + reduce_sum_op(axes=1), width 1
+        y_first.requires_grad_(True)
+        emb, fm = FMLookup.apply(anchor, ids, lookup, lookup_grad, sink)
+        pred = tower(dense, emb.reshape(batch, NFIELD * width), y_first, fm)
+        loss = torch.nn.functional.binary_cross_entropy(pred, label)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        hetu_ops.sgd_update_sparse(first, first_grad.compute(y_first.grad, ids), lr)      # pooled slices: the bag apply
+        hetu_ops.sgd_update_sparse(param, sink.pop("grad"), lr)                            # unpooled slices
+        losses.append(float(loss.detach()))
+        if log_every and (k + 1) % log_every == 0:
+            print("step %d loss %.5f (%.1f ms/step)" % (k + 1, np.mean(losses[-log_every:]),
+                                                        1e3 * (time.perf_counter() - t0) / (k + 1)))
+    torch.cuda.synchronize()
+    return losses, param, tower
+
+
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
-          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False):
+          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False, first_order_init=None):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -269,7 +369,15 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     optimizer (--optimizer): the embedding table's optimizer, --embedding hbm only -- sgd, momentum, nesterov, adagrad, adam or
     adamw with the reference's defaults (momentum 0.9; beta 0.9 / 0.999, eps 1e-7, accumulator from 0, weight decay 0); the
     tower keeps SGD.  opt_fuse_bags=False: the reference's own sequence for it (expanded gradient, deduplicate, the symbol) --
-    the same bits."""
+    the same bits.
+    model="deepfm" (--model deepfm): DeepFM, --embedding hbm with --optimizer sgd only (train_deepfm); first_order_init: its
+    first-order table [rows, 1] (default: N(0, 0.01) from seed + 2), table_init the second-order one."""
+    if model in FM_MODELS:
+        if embedding != "hbm" or optimizer != "sgd":
+            raise ValueError("deepfm runs with --embedding hbm and --optimizer sgd only: its FM-pooled lookup is not part of the "
+                             "step engines, the PS or the cache flows, nor of the other optimizers' pooled paths (got "
+                             "--embedding %s --optimizer %s)" % (embedding, optimizer))
+        return train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every)
     dev = torch.device(device)
     pooled = model in POOLED_MODELS
     if optimizer not in OPTIMIZERS:
@@ -456,8 +564,8 @@ def main():
     # --comm / --cache choose the embedding engine unless --embedding names one (this build's own engines: the HBM-resident
     # table with one launch per step, "queue" = the work-queue step with lookahead, ...).
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo (the reference's names) or "
-                                                   "wdl | dcn | emb_sum_wdl")
+    ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo | deepfm_criteo (the reference's "
+                                                   "names) or wdl | dcn | emb_sum_wdl | deepfm")
     ap.add_argument("-b", "--batch-size", "--batch", dest="batch", type=int, default=256)
     ap.add_argument("-e", "--embedding-size", "--width", dest="width", type=int, default=128)
     ap.add_argument("-r", "--cache-limit-ratio", type=float, default=0.1,
@@ -498,8 +606,8 @@ def main():
     ap.add_argument("--local-shared", action="store_true", help="--laia with the TopkScheduler + shared-memory rings")
     args = ap.parse_args()
     model = args.model[:-len("_criteo")] if args.model.endswith("_criteo") else args.model
-    if model not in ("wdl", "dcn") + POOLED_MODELS:
-        ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, wdl, dcn or emb_sum_wdl")
+    if model not in ("wdl", "dcn") + POOLED_MODELS + FM_MODELS:
+        ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, deepfm_criteo, wdl, dcn, emb_sum_wdl or deepfm")
     args.model = model
     if model in POOLED_MODELS and (args.laia or args.embedding in ("step", "step3", "queue")):
         ap.error("--model %s pools its embeddings: use --embedding hbm (the fused kernel), ps or cache; the step engines "
@@ -515,6 +623,8 @@ def main():
     args.cache = policy
     if args.optimizer != "sgd" and (args.laia or args.embedding != "hbm"):
         ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
+    if model in FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
+        ap.error("--model deepfm runs with --embedding hbm and --optimizer sgd only")
     if args.nepoch > 0:
         args.steps *= args.nepoch
     cache_limit = max(int(args.cache_limit_ratio * args.rows), args.batch * NFIELD)

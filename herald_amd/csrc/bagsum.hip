@@ -185,6 +185,148 @@ __global__ __launch_bounds__(kBagWaves *kWave) void bag_sum2_kernel(
         __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
 }
 
+// FM-pooled lookup (the DeepFM models, examples/ctr/models/deepfm_criteo.py:24-39): one lookup consumed three ways -- as rows
+// (the DNN), as S = sum over the bag and as Q = sum of squares over the bag, combined into 0.5 * (S*S - Q).  bag_sum_kernel
+// with a second accumulator and a row store: per (bag, column)
+//   S  = ((0.0f + r_0) + r_1) + ...                    the chain of bag_sum_kernel, so out_sum is its output bit for bit
+//   Q  = ((0.0f + fl(r_0*r_0)) + fl(r_1*r_1)) + ...    one __fmul_rn and one __fadd_rn per term
+//   fm = fl(0.5f * fl(fl(S*S) - Q))                    three roundings, nothing contracted
+// and out_rows[i,:] = the row of occurrence i (zeros for an id beyond the table), written around the L2 as the gather's; a
+// null out_rows skips the store (the caller already holds the rows: the table IS its row buffer).  Every slice wave of a bag
+// stores its own columns of the bag's rows, so the rows are read once and written once: n * (8 * width + 4) bytes.
+// Registers (ROWS = 32, VEC = 4): 128 for the round's rows, 8 for the two accumulators -- see DESIGN.md for the compiler's
+// counts; no instantiation spills.
+template <typename IdT, int VEC, int ROWS>
+__global__ __launch_bounds__(kBagWaves *kWave) void bag_fm_kernel(
+    const float *__restrict__ table, uint64_t rows, uint32_t width, const IdT *__restrict__ ids, int64_t n, int64_t bag,
+    const int64_t *__restrict__ offsets, int64_t nbags, uint32_t nslice, float *__restrict__ out_rows,
+    float *__restrict__ out_sum, float *__restrict__ out_fm) {
+    typedef typename BagVec<VEC>::T V;
+    const int lane = lane_id();
+    const uint64_t item = static_cast<uint64_t>(blockIdx.x) * kBagWaves + (threadIdx.x >> 6);   // wave-uniform
+    if (item >= static_cast<uint64_t>(nbags) * nslice)
+        return;
+    const int64_t b = static_cast<int64_t>(item / nslice);
+    const uint32_t sl = static_cast<uint32_t>(item - static_cast<uint64_t>(b) * nslice);
+    int64_t lo, hi;
+    if (offsets != nullptr) {
+        lo = offsets[b];
+        hi = offsets[b + 1];
+        lo = lo < 0 ? 0 : (lo > n ? n : lo);
+        hi = hi < lo ? lo : (hi > n ? n : hi);
+    } else {
+        lo = b * bag;
+        hi = lo + bag;      // (n == nbags * bag: checked by the host)
+    }
+    const uint32_t col = (sl * kWave + lane) * VEC;
+    const bool live = col < width;       // (VEC > 1: width % VEC == 0, so a live lane's VEC columns all exist)
+    const uint32_t lcol = live ? col : 0;
+    const bool store_rows = out_rows != nullptr;      // wave-uniform
+    V acc, sq;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        BagVec<VEC>::set(acc, k, 0.f);
+        BagVec<VEC>::set(sq, k, 0.f);
+    }
+    for (int64_t j0 = lo; j0 < hi; j0 += kWave) {
+        const int cnt = static_cast<int>(hi - j0 < kWave ? hi - j0 : kWave);      // ids of this block (wave-uniform)
+        const int64_t j = j0 + (lane < cnt ? lane : cnt - 1);                      // lo <= j < hi <= n
+        const uint64_t r = id_to_row<IdT>(ids[j]);
+        const bool ok = r < rows;
+        const unsigned long long okm = __ballot(ok);
+        const uint64_t off = (ok ? r : 0) * width;          // float offset of the row (row 0 for an id beyond the table)
+        const int off_lo = static_cast<int>(static_cast<uint32_t>(off));
+        const int off_hi = static_cast<int>(static_cast<uint32_t>(off >> 32));
+        for (int c = 0; c < cnt; c += ROWS) {
+            V v[ROWS];
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const int tt = c + t < cnt ? c + t : cnt - 1;
+                const uint64_t o = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(off_hi, tt))) << 32) |
+                                   static_cast<uint32_t>(__builtin_amdgcn_readlane(off_lo, tt));
+                v[t] = *reinterpret_cast<const V *>(table + o + lcol);
+            }
+            __builtin_amdgcn_sched_barrier(0);      // (as bag_sum_kernel: the whole round is requested before the first add)
+#pragma unroll
+            for (int t = 0; t < ROWS; ++t) {
+                const bool in = c + t < cnt;                                  // wave-uniform
+                const bool rok = ((okm >> (in ? c + t : 0)) & 1ull) != 0;     // an id beyond the table is a zero row
+                V row;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const float x = rok ? BagVec<VEC>::get(v[t], k) : 0.f;
+                    BagVec<VEC>::set(row, k, x);
+                    const float a = BagVec<VEC>::get(acc, k);
+                    const float q = BagVec<VEC>::get(sq, k);
+                    const float s = __fadd_rn(a, x);
+                    const float p = __fadd_rn(q, __fmul_rn(x, x));
+                    BagVec<VEC>::set(acc, k, in ? s : a);
+                    BagVec<VEC>::set(sq, k, in ? p : q);
+                }
+                if (store_rows && in && live)      // occurrence j0 + c + t < hi <= n
+                    __builtin_nontemporal_store(
+                        row, reinterpret_cast<V *>(out_rows + static_cast<uint64_t>(j0 + c + t) * width + col));
+            }
+        }
+    }
+    if (live) {
+        V fm;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float s = BagVec<VEC>::get(acc, k);
+            BagVec<VEC>::set(fm, k, __fmul_rn(0.5f, __fsub_rn(__fmul_rn(s, s), BagVec<VEC>::get(sq, k))));
+        }
+        __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out_sum + static_cast<uint64_t>(b) * width + col));
+        __builtin_nontemporal_store(fm, reinterpret_cast<V *>(out_fm + static_cast<uint64_t>(b) * width + col));
+    }
+}
+
+// The per-occurrence gradient of the FM-pooled lookup, one elementwise launch:
+//   out[i,c] = fl( fl(g_rows[i,c] + fl(g_fm[b,c] * sum[b,c])) - fl(g_fm[b,c] * emb_rows[i,c]) ),   b = the bag of i
+// (g_rows null: out = fl(fl(g_fm*sum) - fl(g_fm*emb_rows))).  The lookup's output has three consumers -- the rows, S and Q --
+// and the reference's executor adds their adjoints g_rows, g_fm*S and -g_fm*e in its topological order, which is specified
+// nowhere; the order above is this project's fixed one, as the bag sum's is.  out may alias g_rows: a thread reads its own
+// elements before it writes them.  A thread handles one vector of VEC floats; nv = width / VEC.
+template <int VEC>
+__global__ __launch_bounds__(256) void fm_grad_rows_kernel(const float *g_rows, const float *__restrict__ emb_rows,
+                                                           const float *__restrict__ sum, const float *__restrict__ g_fm,
+                                                           uint64_t total_vec, uint32_t nv, uint32_t bag,
+                                                           const int32_t *__restrict__ bag_of, uint32_t nbags, float *out) {
+    typedef typename BagVec<VEC>::T V;
+    const uint64_t e = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= total_vec)
+        return;
+    uint64_t i;
+    if (total_vec <= 0xFFFFFFFFull)      // (uniform: the 32-bit division)
+        i = static_cast<uint32_t>(e) / nv;
+    else
+        i = e / nv;
+    const uint32_t cv = static_cast<uint32_t>(e - i * nv);
+    uint32_t b;      // i < n < 2^31 (checked by the host)
+    if (bag_of != nullptr)
+        b = static_cast<uint32_t>(bag_of[i]);
+    else
+        b = static_cast<uint32_t>(i) / bag;
+    b = b < nbags ? b : nbags - 1;       // (ha_bag_of's entries are in [0, nbags): no row beyond sum / g_fm is read whatever bag_of holds)
+    const uint64_t bo = (static_cast<uint64_t>(b) * nv + cv) * VEC;
+    const V ev = *reinterpret_cast<const V *>(emb_rows + e * VEC);
+    const V sv = *reinterpret_cast<const V *>(sum + bo);
+    const V gf = *reinterpret_cast<const V *>(g_fm + bo);
+    V gr = sv;      // (not used without g_rows)
+    if (g_rows != nullptr)
+        gr = *reinterpret_cast<const V *>(g_rows + e * VEC);
+    V o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const float f = BagVec<VEC>::get(gf, k);
+        float a = __fmul_rn(f, BagVec<VEC>::get(sv, k));
+        if (g_rows != nullptr)
+            a = __fadd_rn(BagVec<VEC>::get(gr, k), a);
+        BagVec<VEC>::set(o, k, __fsub_rn(a, __fmul_rn(f, BagVec<VEC>::get(ev, k))));
+    }
+    *reinterpret_cast<V *>(out + e * VEC) = o;
+}
+
 // bag_of[i] = the bag of occurrence i: the largest b in [0, nbags) with offsets[b] <= i (empty bags are skipped).  Always in
 // [0, nbags), whatever offsets holds; offsets[0] and offsets[nbags] are not read.
 __global__ __launch_bounds__(256) void bag_of_kernel(const int64_t *__restrict__ offsets, int nbags, int64_t n,
@@ -325,6 +467,89 @@ static int bag_sum2_launch(const float *table, int64_t rows, const float *recv, 
     return 0;
 }
 
+// ha_gather_fm_*: the checks of bag_sum_launch (before any device access), the same launch rule and rows per round.
+template <typename IdT>
+static int bag_fm_launch(const char *what, const float *table, int64_t rows, int64_t width, const IdT *ids, int64_t n,
+                         int64_t bag, const int64_t *offsets, int64_t nbags, float *out_rows, float *out_sum, float *out_fm,
+                         hipStream_t stream) {
+    HA_REQUIRE(rows >= 0 && width >= 1 && width < (1ll << 30) && n >= 0 && nbags >= 0 && bag >= 0,
+               "%s: bad sizes rows=%ld width=%ld n=%ld bag=%ld nbags=%ld", what, (long)rows, (long)width, (long)n, (long)bag,
+               (long)nbags);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "%s: give exactly one of bag >= 1 and offsets (bag=%ld, offsets %s)", what,
+               (long)bag, offsets ? "given" : "null");
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+               (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(nbags == 0 || (out_sum != nullptr && out_fm != nullptr), "%s: null out_sum or out_fm", what);
+    if (nbags == 0)
+        return 0;
+    HA_REQUIRE(table != nullptr, "%s: null table", what);
+    HA_REQUIRE(ids != nullptr || n == 0, "%s: null ids", what);
+    const size_t pooled_bytes = static_cast<size_t>(nbags) * width * sizeof(float);
+    if (rows == 0) {      // every id is beyond the table (and there is no row 0 for the clamped loads to read)
+        HA_CHECK_HIP(hipMemsetAsync(out_sum, 0, pooled_bytes, stream));
+        HA_CHECK_HIP(hipMemsetAsync(out_fm, 0, pooled_bytes, stream));
+        if (out_rows != nullptr && n > 0)
+            HA_CHECK_HIP(hipMemsetAsync(out_rows, 0, static_cast<size_t>(n) * width * sizeof(float), stream));
+        return 0;
+    }
+    // (ragged bags: an occurrence outside every clamped bag belongs to no bag -- offsets[0] > 0, offsets[nbags] < n -- and
+    // its row is not written)
+    const bool vec_ok = (width % 4 == 0) && (reinterpret_cast<uintptr_t>(table) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(out_sum) % 16 == 0) && (reinterpret_cast<uintptr_t>(out_fm) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(out_rows) % 16 == 0);
+    BagLaunchRule lr;
+    if (bag_launch_rule(what, vec_ok, width, n, bag, offsets, nbags, &lr))
+        return -1;
+    const dim3 grid(lr.blocks), block(kBagWaves * kWave);
+#define HA_FM_CASE(V, R)                                                                                               \
+    hipLaunchKernelGGL((bag_fm_kernel<IdT, V, R>), grid, block, 0, stream, table, (uint64_t)rows, (uint32_t)width, ids, n, \
+                       bag, offsets, nbags, lr.nslice, out_rows, out_sum, out_fm)
+    if (lr.vec == 4) {
+        if (lr.few) HA_FM_CASE(4, 8); else HA_FM_CASE(4, 32);
+    } else if (lr.vec == 2) {
+        if (lr.few) HA_FM_CASE(2, 8); else HA_FM_CASE(2, 32);
+    } else {
+        if (lr.few) HA_FM_CASE(1, 8); else HA_FM_CASE(1, 32);
+    }
+#undef HA_FM_CASE
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
+static int fm_grad_rows_launch(const float *g_rows, const float *emb_rows, const float *sum, const float *g_fm, int64_t n,
+                               int64_t width, int64_t bag, const int32_t *bag_of, int64_t nbags, float *out,
+                               hipStream_t stream) {
+    const char *what = "ha_fm_grad_rows";
+    HA_REQUIRE(n >= 0 && n < (1ll << 31) && width >= 1 && width < (1ll << 30) && bag >= 0 && nbags >= 0 && nbags < (1ll << 31),
+               "%s: bad sizes n=%ld width=%ld bag=%ld nbags=%ld", what, (long)n, (long)width, (long)bag, (long)nbags);
+    HA_REQUIRE((bag >= 1) != (bag_of != nullptr), "%s: give exactly one of bag >= 1 and bag_of (bag=%ld, bag_of %s)", what,
+               (long)bag, bag_of ? "given" : "null");
+    HA_REQUIRE(bag_of != nullptr || (n % bag == 0 && n / bag == nbags), "%s: n=%ld is not nbags=%ld bags of bag=%ld ids", what,
+               (long)n, (long)nbags, (long)bag);
+    if (n == 0)
+        return 0;
+    HA_REQUIRE(nbags >= 1, "%s: %ld occurrences in no bag", what, (long)n);
+    HA_REQUIRE(emb_rows && sum && g_fm && out, "%s: null pointer", what);
+    HA_REQUIRE(out != emb_rows && out != sum && out != g_fm, "%s: out may alias g_rows only", what);
+    const bool vec_ok = (width % 4 == 0) &&
+                        ((reinterpret_cast<uintptr_t>(g_rows) | reinterpret_cast<uintptr_t>(emb_rows) |
+                          reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(g_fm) |
+                          reinterpret_cast<uintptr_t>(out)) % 16 == 0);
+    const int vec = vec_ok ? 4 : 1;
+    const uint64_t total_vec = static_cast<uint64_t>(n) * static_cast<uint64_t>(width / vec);
+    const uint64_t blocks64 = (total_vec + 255) / 256;      // sized by the work: n * width elements
+    HA_REQUIRE(blocks64 < (1ull << 31), "%s: batch too large", what);
+    const dim3 grid(static_cast<unsigned>(blocks64)), block(256);
+    if (vec == 4)
+        hipLaunchKernelGGL((fm_grad_rows_kernel<4>), grid, block, 0, stream, g_rows, emb_rows, sum, g_fm, total_vec,
+                           (uint32_t)(width / 4), (uint32_t)bag, bag_of, (uint32_t)nbags, out);
+    else
+        hipLaunchKernelGGL((fm_grad_rows_kernel<1>), grid, block, 0, stream, g_rows, emb_rows, sum, g_fm, total_vec,
+                           (uint32_t)width, (uint32_t)bag, bag_of, (uint32_t)nbags, out);
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+
 int scratch_get(hipStream_t stream, size_t bytes, void **out);   // capi.hip
 
 template <typename IdT>
@@ -371,7 +596,27 @@ extern "C" int ha_gather_sum_u64ids(const float *table, int64_t rows, int64_t wi
                                         ha::as_stream(stream));
 }
 
-// The same over a buffer of rows named by uint32 keys held in device memory (the sharded store's pull: rows_buf = the unique rows
+extern "C" int ha_gather_fm_f32ids(const float *table, int64_t rows, int64_t width, const float *ids, int64_t n, int64_t bag,
+                                   const int64_t *offsets, int64_t nbags, float *out_rows, float *out_sum, float *out_fm,
+                                   ha_stream_t stream) {
+    return ha::bag_fm_launch<float>("ha_gather_fm_f32ids", table, rows, width, ids, n, bag, offsets, nbags, out_rows, out_sum,
+                                    out_fm, ha::as_stream(stream));
+}
+
+extern "C" int ha_gather_fm_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
+                                   const int64_t *offsets, int64_t nbags, float *out_rows, float *out_sum, float *out_fm,
+                                   ha_stream_t stream) {
+    return ha::bag_fm_launch<uint64_t>("ha_gather_fm_u64ids", table, rows, width, ids, n, bag, offsets, nbags, out_rows, out_sum,
+                                       out_fm, ha::as_stream(stream));
+}
+
+extern "C" int ha_fm_grad_rows(const float *g_rows, const float *emb_rows, const float *sum, const float *g_fm, int64_t n,
+                               int64_t width, int64_t bag, const int32_t *bag_of, int64_t nbags, float *out,
+                               ha_stream_t stream) {
+    return ha::fm_grad_rows_launch(g_rows, emb_rows, sum, g_fm, n, width, bag, bag_of, nbags, out, ha::as_stream(stream));
+}
+
+// ha_gather_sum_* over a buffer of rows named by uint32 keys held in device memory (the sharded store's pull: rows_buf = the unique rows
 // a batch received, keys = its plan's inverse[n]) -- the expand to [n, width] and the sum over it in one pass.
 extern "C" int ha_gather_sum_u32keys(const float *rows_buf, int64_t rows, int64_t width, const uint32_t *keys, int64_t n,
                                      int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream) {

@@ -5,6 +5,9 @@ Mirrors (paths relative to /root/reference):
   EmbeddingLookUp / EmbeddingLookUp_Gradient      python/hetu/gpu_ops/EmbeddingLookUp.py:10-125
   EmbeddingLookUpSum / EmbeddingLookUpSum_Gradient  the same followed by reduce_sum_op(axes=1), python/hetu/gpu_ops/ReduceSum.py
                                                   (examples/ctr/models/emb_sum_*.py)
+  EmbeddingLookUpFM / EmbeddingLookUpFM_Gradient  one lookup consumed as rows, as reduce_sum_op(axes=1) and as
+                                                  reduce_sum_op(mul_op(e, e), axes=1): the second-order term of the DeepFM models
+                                                  (examples/ctr/models/deepfm_criteo.py:24-39)
   ParameterServerCommunicateOp                    python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
   ParameterServerSparsePullOp                     python/hetu/gpu_ops/ParameterServerCommunicate.py:254-306
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
@@ -206,6 +209,63 @@ class EmbeddingLookUpSum_Gradient:
                                      bag=index.shape[1])
         return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
                                  bag_of=ops.bag_of(offsets, index.numel()), offsets=offsets)
+
+
+class EmbeddingLookUpFM(EmbeddingLookUp):
+    """embedding_lookup_op(embedding, index) consumed three ways, the second-order term of the reference's DeepFM models
+    (examples/ctr/models/deepfm_criteo.py:24-39): as rows (the DNN), as reduce_sum_op(axes=1) and as
+    reduce_sum_op(mul_op(e, e), axes=1), the last two combined into 0.5 * (S*S - Q).
+    compute(ids[B, F], output_val[B, F, width], sum_val[B, width], fm_val[B, width]) -- or ids[n], output_val[n, width] with
+    offsets[B + 1] for ragged bags.  With a device table it is the fused kernel (ops.embedding_lookup_fm): rows read once,
+    written once.  On the PS, cache and prefetched paths the rows arrive in output_val exactly as EmbeddingLookUp delivers them
+    and the same kernel runs over that buffer as a table (ids 0 .. n-1, no row store): every path agrees bit for bit on equal
+    rows."""
+
+    def forward_hook(self, config):
+        super().forward_hook(config)
+        self._rows_compute = self.compute
+        self._fused = self._rows_compute == self._compute_gpu
+        self._pos = None
+        self.compute = self._compute_fm
+
+    def _compute_fm(self, ids, output_val, sum_val, fm_val, stream=None, offsets=None):
+        if self._fused:
+            ops.embedding_lookup_fm(self.embedding.table, ids, offsets=offsets, rows_out=output_val, sum_out=sum_val,
+                                    fm_out=fm_val, stream=stream)
+            return output_val, sum_val, fm_val
+        n, width = ids.numel(), self.embedding.shape[1]
+        if self._pos is None or self._pos.numel() < n or self._pos.device != output_val.device:
+            self._pos = torch.arange(max(n, 1), dtype=torch.int64, device=output_val.device)
+        self._rows_compute(ids, output_val, stream)
+        ops.embedding_lookup_fm(output_val.view(n, width), self._pos[:n].view(ids.shape), offsets=offsets, sum_out=sum_val,
+                                fm_out=fm_val, want_rows=False, stream=stream)
+        return output_val, sum_val, fm_val
+
+
+class EmbeddingLookUpFM_Gradient:
+    """The gradient of EmbeddingLookUpFM: the adjoints of the lookup's three consumers -- `vectors` (the gradient of the rows, or
+    None when nothing consumed them) and `fm_grad` (the gradient of the FM output) with the forward's `rows` and `sum` -- are
+    combined per occurrence by one launch (ops.fm_grad_rows, in place over `vectors` when given) and wrapped as ordinary
+    UNPOOLED IndexedSlices: sgd_update_sparse, the fused optimizers and ParameterServerCommunicateOp take them as they take
+    EmbeddingLookUp_Gradient's.  Push indices are handled as there."""
+
+    def __init__(self, embed_shape, enable_push_index=False):
+        self.embed_shape, self.enable_push_index = embed_shape, enable_push_index
+
+    def compute(self, vectors, fm_grad, rows, sum, index, offsets=None, stream=None):
+        push = None
+        if isinstance(index, tuple):
+            index, push = index[0], (index[1] if self.enable_push_index else None)
+        elif self.enable_push_index:
+            raise TypeError
+        if offsets is None:
+            if index.dim() != 2:
+                raise ValueError("fixed bags need an index of shape [B, F]; give offsets for ragged bags")
+            values = ops.fm_grad_rows(vectors, rows, sum, fm_grad, bag=index.shape[1], out=vectors, stream=stream)
+        else:
+            values = ops.fm_grad_rows(vectors, rows, sum, fm_grad, bag_of=ops.bag_of(offsets, index.numel(), stream=stream),
+                                      out=vectors, stream=stream)
+        return ops.IndexedSlices(indices=index, values=values, dense_shape=self.embed_shape, push_indices=push)
 
 
 def sgd_update_sparse(param, grad, lr, stream=None):

@@ -353,6 +353,81 @@ def embedding_lookup_sum(table, ids, offsets=None, out=None, stream=None):
     return out
 
 
+def embedding_lookup_fm(table, ids, offsets=None, rows_out=None, sum_out=None, fm_out=None, want_rows=True, stream=None):
+    """FM-pooled lookup (ha_gather_fm_*), the second-order term of the DeepFM models: one pass over the rows of bag b's ids
+    gives rows[..., :] (what embedding_lookup gives), sum[b, :] = S (what embedding_lookup_sum gives, bit for bit) and
+    fm[b, :] = 0.5 * (S*S - Q) with Q the position-ordered sum of the squared rows -- every product, sum and difference rounded
+    on its own.  ids / offsets as in embedding_lookup_sum.  want_rows=False: the rows are not written (the caller holds them:
+    `table` is its row buffer).  Ragged bags: the row of an occurrence that lies in no bag is not written.
+    Returns (rows [ids.shape + (width,)] or None, sum [B, width], fm [B, width])."""
+    L = _lib.load()
+    _require(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    width = table.shape[1]
+    if not want_rows:
+        if rows_out is not None:
+            raise ValueError("rows_out comes with want_rows=True")
+    elif rows_out is None:
+        rows_out = torch.empty(tuple(ids.shape) + (width,), dtype=torch.float32, device=table.device)
+    if sum_out is None:
+        sum_out = torch.empty((nbags, width), dtype=torch.float32, device=table.device)
+    if fm_out is None:
+        fm_out = torch.empty((nbags, width), dtype=torch.float32, device=table.device)
+    for name, t, numel in (("rows_out", rows_out, n * width), ("sum_out", sum_out, nbags * width),
+                           ("fm_out", fm_out, nbags * width)):
+        if t is None:
+            continue
+        _require(t, torch.float32, name)
+        if t.numel() != numel:
+            raise ValueError("%s has the wrong size" % name)
+    fn = _ids_fn(ids, L.ha_gather_fm_f32ids, L.ha_gather_fm_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), n, bag, _ptr(offsets) if offsets is not None else None, nbags,
+             _ptr(rows_out) if rows_out is not None else None, _ptr(sum_out), _ptr(fm_out), _stream_ptr(stream)),
+          "ha_gather_fm")
+    return rows_out, sum_out, fm_out
+
+
+def fm_grad_rows(g_rows, emb_rows, sum, g_fm, bag=None, bag_of=None, out=None, stream=None):
+    """The per-occurrence gradient of embedding_lookup_fm (ha_fm_grad_rows): out[i, :] = (g_rows[i, :] + g_fm[b, :] * sum[b, :])
+    - g_fm[b, :] * emb_rows[i, :] with b the bag of occurrence i, in that order, every operation rounded on its own (the order
+    is this project's fixed choice; the reference's is unspecified).  g_rows: the gradient of the rows, or None when nothing
+    consumed them.  emb_rows [..., width] and sum [B, width] are the forward's outputs, g_fm [B, width] the gradient of fm.
+    Give `bag` (fixed bags of that many ids) or `bag_of` (int32 [n], from ops.bag_of).  out: default a new tensor shaped as
+    emb_rows; it may be g_rows itself (in place).  Returns out, an ordinary unpooled gradient."""
+    _require(emb_rows, torch.float32, "emb_rows")
+    _require(sum, torch.float32, "sum")
+    _require(g_fm, torch.float32, "g_fm")
+    if sum.dim() != 2 or tuple(g_fm.shape) != tuple(sum.shape):
+        raise ValueError("sum and g_fm must both be [B, width]")
+    nbags, width = sum.shape
+    if emb_rows.dim() < 1 or emb_rows.shape[-1] != width:
+        raise ValueError("emb_rows must be [..., %d]" % width)
+    n = emb_rows.numel() // width
+    if g_rows is not None:
+        _require(g_rows, torch.float32, "g_rows")
+        if g_rows.numel() != n * width:
+            raise ValueError("g_rows must have the size of emb_rows")
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != n:
+            raise ValueError("bag_of must have one entry per occurrence")
+    elif bag < 1 or n != nbags * bag:
+        raise ValueError("emb_rows must hold B * bag rows")
+    if out is None:
+        out = torch.empty_like(emb_rows)
+    _require(out, torch.float32, "out")
+    if out.numel() != n * width:
+        raise ValueError("out has the wrong size")
+    check(_lib.load().ha_fm_grad_rows(_ptr(g_rows) if g_rows is not None else None, _ptr(emb_rows), _ptr(sum), _ptr(g_fm), n,
+                                      width, int(bag) if bag is not None else 0, _ptr(bag_of) if bag_of is not None else None,
+                                      nbags, _ptr(out), _stream_ptr(stream)), "ha_fm_grad_rows")
+    return out
+
+
 def gather_sum_u32keys(rows_buf, keys_i32, bag=None, offsets=None, out=None, stream=None):
     """embedding_lookup_sum over a buffer of rows named by uint32 keys held in an int32 tensor (a plan's inverse(): the pull
     of the sharded store sums a batch's bags straight out of the unique rows it received).  Fixed bags: keys [B, F], or

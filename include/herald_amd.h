@@ -1428,6 +1428,38 @@ int ha_momentum_sparse_update_bags_f32ids(float *param, int64_t rows, int64_t wi
 int ha_momentum_sparse_update_bags_u64ids(float *param, int64_t rows, int64_t width, const uint64_t *ids, int64_t n,
                                           const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
                                           float *velocity, float lr, float momentum, int nesterov, ha_stream_t stream);
+/* FM-pooled lookup: the second-order term of the reference's DeepFM models (examples/ctr/models/deepfm_criteo.py:24-39),
+ * where one lookup is consumed as rows (the DNN), as reduce_sum_op(axes=1) and as reduce_sum_op(mul_op(e, e), axes=1).
+ * Bags -- fixed or ragged, exactly one of bag >= 1 and offsets, offsets clamped -- are those of ha_gather_sum_*.  Per bag b
+ * and column c, with r_j the table rows of the bag's ids in position order:
+ *   out_sum[b,c] = S = ((0.0f + r_0) + r_1) + ...                   the chain of ha_gather_sum_*: the same bits
+ *   Q                = ((0.0f + fl(r_0*r_0)) + fl(r_1*r_1)) + ...   one multiply and one add per term, each rounded
+ *   out_fm[b,c]      = fl(0.5f * fl(fl(S*S) - Q))                   three roundings, nothing contracted
+ *   out_rows[i,:]    = the row of occurrence i ([n, width]), as ha_gather_* writes it
+ * An id >= rows is a zero row in all three outputs; an empty bag gives zeros in out_sum and out_fm.  out_rows may be NULL
+ * (the caller holds the rows already: `table` is its [n, width] row buffer and ids are 0 .. n-1).  Ragged bags: the row of
+ * an occurrence that lies in no bag (before offsets[0] or at / beyond offsets[nbags]) is not written.  Any width >= 1;
+ * width % 4 == 0 with 16-byte aligned table / outputs takes the 16-byte path.  Rows read once, written once:
+ * n * (8 * width + 4) bytes.  Arguments are checked before any device access (out_sum and out_fm must not be NULL). */
+int ha_gather_fm_f32ids(const float *table, int64_t rows, int64_t width, const float *ids, int64_t n, int64_t bag,
+                        const int64_t *offsets, int64_t nbags, float *out_rows, float *out_sum, float *out_fm,
+                        ha_stream_t stream);
+int ha_gather_fm_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
+                        const int64_t *offsets, int64_t nbags, float *out_rows, float *out_sum, float *out_fm,
+                        ha_stream_t stream);
+/* Its backward, one elementwise launch: the per-occurrence gradient [n, width] from the adjoints of the three consumers,
+ *   out[i,c] = fl( fl(g_rows[i,c] + fl(g_fm[b,c] * sum[b,c])) - fl(g_fm[b,c] * emb_rows[i,c]) ),   b = the bag of i.
+ * g_rows [n, width]: the gradient of out_rows, or NULL when nothing consumed the rows -- then
+ *   out = fl(fl(g_fm*sum) - fl(g_fm*emb_rows)).
+ * g_fm, sum [nbags, width]: the gradient of out_fm and the forward's out_sum; emb_rows [n, width]: the forward's out_rows.
+ * The reference's executor adds the three adjoints in its topological order, which is specified nowhere: the order above is
+ * this project's fixed choice (as the bag sum's order is), the same on every path here.  Fixed bags: bag >= 1, bag_of NULL,
+ * n == nbags * bag, b = i / bag in registers; ragged bags: bag == 0 and bag_of = int32[n] from ha_bag_of -- exactly one of
+ * the two, as ha_sgd_apply_bags.  out may alias g_rows (in place) and nothing else.  The result is an ordinary unpooled
+ * gradient: ha_sgd_apply, the fused optimizers and the PS / cache pushes take it as they take any [n, width] gradient.
+ * width % 4 == 0 with every pointer 16-byte aligned takes 16-byte accesses.  Checked before any device access. */
+int ha_fm_grad_rows(const float *g_rows, const float *emb_rows, const float *sum, const float *g_fm, int64_t n,
+                    int64_t width, int64_t bag, const int32_t *bag_of, int64_t nbags, float *out, ha_stream_t stream);
 /* Measurement aid (tools/bag_bench.py): column-slice width of ha_gather_sum_*'s 16-byte path, 64 / 128 / 256 floats per
  * wave; 0 = chosen from the batch (the default).  Process-wide; results do not depend on it. */
 int ha_debug_bag_slice(int floats);
