@@ -52,6 +52,10 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      the DNN (rows), the sum S and the sum of squares Q -- the fused FM-pooled lookup (ha_gather_fm_*) writes
                      rows, S and 0.5 * (S*S - Q) in one pass, ha_fm_grad_rows combines the gradients of the rows and of the FM
                      output into one per-occurrence gradient for the ordinary sparse SGD.  --embedding hbm, --optimizer sgd.
+  --model emb_sum_deepfm  the pooled DeepFM (examples/ctr/models/emb_sum_deepfm_avazu.py; also emb_sum_deepfm_avazu,
+                     emb_sum_dfm_avazu): the second-order lookup is consumed only as S (the DNN's input and S*S) and Q, so the
+                     lookup writes no rows (ha_gather_fm_* with out_rows NULL) and its whole backward is ONE fused apply
+                     (ha_sgd_sparse_update_fm_bags_*): no [batch * 26, d] tensor in the step.  --embedding hbm, --optimizer sgd.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -178,13 +182,59 @@ class FMLookup(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class SumFMTower(torch.nn.Module):
+    """The dense part of emb_sum_deepfm_avazu (models/emb_sum_deepfm_avazu.py; the same shape in fae_deepfm_avazu.py): FM_W
+    [13, 1] for the first-order dense part and the DNN d-256-256-1 over S, the SUM of a sample's second-order rows; every
+    weight ~ N(0, 0.01).  forward(dense, total [B, d] = S, first [B, 1], fm [B, d] = 0.5 * (S*S - Q)):
+    y = sigmoid((y1 + y2) + y3) as FMTower."""
+
+    def __init__(self, width, seed=0):
+        super().__init__()
+        g = torch.Generator().manual_seed(seed)
+
+        def w(*shape):
+            return torch.nn.Parameter(torch.randn(*shape, generator=g) * 0.01)
+        self.FM_W = w(NDENSE, 1)
+        self.W1, self.W2, self.W3 = w(width, 256), w(256, 256), w(256, 1)
+
+    def forward(self, dense, total, first, fm):
+        y1 = dense @ self.FM_W + first
+        y2 = fm.sum(1, keepdim=True)
+        y3 = torch.relu(torch.relu(total @ self.W1) @ self.W2) @ self.W3
+        return torch.sigmoid((y1 + y2) + y3)
+
+
+class FMSumLookup(torch.autograd.Function):
+    """EmbeddingLookUpFMSum and EmbeddingLookUpFMSum_Gradient as one autograd node: forward returns S [B, d] and the FM output
+    [B, d] of one fused lookup that writes no rows; backward wraps the gradients of both with S as FM-pooled IndexedSlices in
+    `sink` -- nothing [B * 26, d] is saved or built.  `anchor` as in FMLookup."""
+
+    @staticmethod
+    def forward(ctx, anchor, ids, lookup, lookup_grad, sink):
+        batch, width = ids.shape[0], lookup.embedding.shape[1]
+        total = torch.empty((batch, width), dtype=torch.float32, device=ids.device)
+        fm = torch.empty((batch, width), dtype=torch.float32, device=ids.device)
+        lookup.compute(ids, total, fm)
+        ctx.save_for_backward(ids, total)
+        ctx.lookup_grad, ctx.sink = lookup_grad, sink
+        return total, fm
+
+    @staticmethod
+    def backward(ctx, g_total, g_fm):
+        ids, total = ctx.saved_tensors
+        ctx.sink["grad"] = ctx.lookup_grad.compute(g_total.contiguous(), g_fm.contiguous(), total, ids)
+        return None, None, None, None, None
+
+
 POOLED_MODELS = ("emb_sum_wdl",)
-FM_MODELS = ("deepfm",)
+FM_MODELS = ("deepfm", "emb_sum_deepfm")
+MODEL_ALIASES = {"emb_sum_deepfm_avazu": "emb_sum_deepfm", "emb_sum_dfm_avazu": "emb_sum_deepfm"}
 OPTIMIZERS = ("sgd", "momentum", "nesterov", "adagrad", "adam", "adamw")
 
 
 def make_tower(model, width, seed=0):
-    return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower, "deepfm": FMTower}[model](width, seed)
+    return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower, "deepfm": FMTower,
+            "emb_sum_deepfm": SumFMTower}[model](width, seed)
 
 
 def make_samples(nsamples, rows, seed=0):
@@ -299,12 +349,15 @@ def make_batches(nbatch, batch, rows, seed=0, rank=0, world=1):
     return out
 
 
-def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every):
+def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every, model="deepfm"):
     """--model deepfm with both tables in HBM: the first-order table [rows, 1] through EmbeddingLookUpSum and the pooled SGD
-    apply, the second-order table [rows, width] through the FM operator pair (FMLookup) and the unpooled sparse SGD.  Returns
-    (losses, second-order parameter, tower); the first-order parameter is `parameter.first_order`."""
+    apply, the second-order table [rows, width] through the FM operator pair (FMLookup) and the unpooled sparse SGD.
+    --model emb_sum_deepfm: the second-order table through the pooled pair (FMSumLookup: S and the FM output, no rows) and
+    the fused FM apply of FM-pooled slices.  Returns (losses, second-order parameter, tower); the first-order parameter is
+    `parameter.first_order`."""
     dev = torch.device(device)
-    tower = make_tower("deepfm", width, seed).to(dev)
+    pooled = model == "emb_sum_deepfm"
+    tower = make_tower(model, width, seed).to(dev)
     opt = torch.optim.SGD(tower.parameters(), lr=lr)
     dev_batches = [tuple(torch.from_numpy(a).to(dev) for a in b) for b in make_batches(min(steps + 1, 64), batch, rows, seed)]
     if table_init is None:
@@ -319,9 +372,9 @@ def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_
     first_lookup = hetu_ops.EmbeddingLookUpSum(first)
     first_lookup.forward_hook(config)
     first_grad = hetu_ops.EmbeddingLookUpSum_Gradient(first.shape)
-    lookup = hetu_ops.EmbeddingLookUpFM(param)
+    lookup = (hetu_ops.EmbeddingLookUpFMSum if pooled else hetu_ops.EmbeddingLookUpFM)(param)
     lookup.forward_hook(config)
-    lookup_grad = hetu_ops.EmbeddingLookUpFM_Gradient(param.shape)
+    lookup_grad = (hetu_ops.EmbeddingLookUpFMSum_Gradient if pooled else hetu_ops.EmbeddingLookUpFM_Gradient)(param.shape)
     anchor = torch.zeros((), device=dev, requires_grad=True)
     sink = {}
     losses = []
@@ -331,14 +384,18 @@ def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_
         y_first = torch.empty((batch, 1), dtype=torch.float32, device=dev)
         first_lookup.compute(ids, y_first)                         # embedding_lookup_op + reduce_sum_op(axes=1), width 1
         y_first.requires_grad_(True)
-        emb, fm = FMLookup.apply(anchor, ids, lookup, lookup_grad, sink)
-        pred = tower(dense, emb.reshape(batch, NFIELD * width), y_first, fm)
+        if pooled:
+            total, fm = FMSumLookup.apply(anchor, ids, lookup, lookup_grad, sink)
+            pred = tower(dense, total, y_first, fm)
+        else:
+            emb, fm = FMLookup.apply(anchor, ids, lookup, lookup_grad, sink)
+            pred = tower(dense, emb.reshape(batch, NFIELD * width), y_first, fm)
         loss = torch.nn.functional.binary_cross_entropy(pred, label)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
         hetu_ops.sgd_update_sparse(first, first_grad.compute(y_first.grad, ids), lr)      # pooled slices: the bag apply
-        hetu_ops.sgd_update_sparse(param, sink.pop("grad"), lr)                            # unpooled slices
+        hetu_ops.sgd_update_sparse(param, sink.pop("grad"), lr)              # unpooled slices, or FM-pooled: the fused FM apply
         losses.append(float(loss.detach()))
         if log_every and (k + 1) % log_every == 0:
             print("step %d loss %.5f (%.1f ms/step)" % (k + 1, np.mean(losses[-log_every:]),
@@ -374,10 +431,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     first-order table [rows, 1] (default: N(0, 0.01) from seed + 2), table_init the second-order one."""
     if model in FM_MODELS:
         if embedding != "hbm" or optimizer != "sgd":
-            raise ValueError("deepfm runs with --embedding hbm and --optimizer sgd only: its FM-pooled lookup is not part of the "
+            raise ValueError("%s runs with --embedding hbm and --optimizer sgd only: its FM-pooled lookup is not part of the "
                              "step engines, the PS or the cache flows, nor of the other optimizers' pooled paths (got "
-                             "--embedding %s --optimizer %s)" % (embedding, optimizer))
-        return train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every)
+                             "--embedding %s --optimizer %s)" % (model, embedding, optimizer))
+        return train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every, model)
     dev = torch.device(device)
     pooled = model in POOLED_MODELS
     if optimizer not in OPTIMIZERS:
@@ -564,8 +621,9 @@ def main():
     # --comm / --cache choose the embedding engine unless --embedding names one (this build's own engines: the HBM-resident
     # table with one launch per step, "queue" = the work-queue step with lookahead, ...).
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo | deepfm_criteo (the reference's "
-                                                   "names) or wdl | dcn | emb_sum_wdl | deepfm")
+    ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo | deepfm_criteo | "
+                                                   "emb_sum_deepfm_avazu | emb_sum_dfm_avazu (the reference's names) or "
+                                                   "wdl | dcn | emb_sum_wdl | deepfm | emb_sum_deepfm")
     ap.add_argument("-b", "--batch-size", "--batch", dest="batch", type=int, default=256)
     ap.add_argument("-e", "--embedding-size", "--width", dest="width", type=int, default=128)
     ap.add_argument("-r", "--cache-limit-ratio", type=float, default=0.1,
@@ -605,9 +663,10 @@ def main():
     ap.add_argument("--laia", action="store_true", help="the laia-scheduled loop of run_laia.py (cache over the sharded table)")
     ap.add_argument("--local-shared", action="store_true", help="--laia with the TopkScheduler + shared-memory rings")
     args = ap.parse_args()
-    model = args.model[:-len("_criteo")] if args.model.endswith("_criteo") else args.model
+    model = args.model[:-len("_criteo")] if args.model.endswith("_criteo") else MODEL_ALIASES.get(args.model, args.model)
     if model not in ("wdl", "dcn") + POOLED_MODELS + FM_MODELS:
-        ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, deepfm_criteo, wdl, dcn, emb_sum_wdl or deepfm")
+        ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, deepfm_criteo, emb_sum_deepfm_avazu, "
+                 "emb_sum_dfm_avazu, wdl, dcn, emb_sum_wdl, deepfm or emb_sum_deepfm")
     args.model = model
     if model in POOLED_MODELS and (args.laia or args.embedding in ("step", "step3", "queue")):
         ap.error("--model %s pools its embeddings: use --embedding hbm (the fused kernel), ps or cache; the step engines "
@@ -624,7 +683,7 @@ def main():
     if args.optimizer != "sgd" and (args.laia or args.embedding != "hbm"):
         ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
     if model in FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
-        ap.error("--model deepfm runs with --embedding hbm and --optimizer sgd only")
+        ap.error("--model %s runs with --embedding hbm and --optimizer sgd only" % model)
     if args.nepoch > 0:
         args.steps *= args.nepoch
     cache_limit = max(int(args.cache_limit_ratio * args.rows), args.batch * NFIELD)

@@ -230,6 +230,9 @@ def _declare(L):
         "ha_gather_fm_f32ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp],
         "ha_gather_fm_u64ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, vp],
         "ha_fm_grad_rows": [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp],
+        "ha_sgd_apply_fm_bags": [vp, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, f32, vp],
+        "ha_sgd_sparse_update_fm_bags_f32ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, f32, vp],
+        "ha_sgd_sparse_update_fm_bags_u64ids": [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, f32, vp],
         "ha_debug_bag_slice": [c.c_int],
         "ha_lookup_sort_f32ids": [vp, i64, i64, vp, i64, vp, vp, vp],
         "ha_lookup_sort_u64ids": [vp, i64, i64, vp, i64, vp, vp, vp],

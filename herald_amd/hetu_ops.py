@@ -8,7 +8,10 @@ Mirrors (paths relative to /root/reference):
   EmbeddingLookUpFM / EmbeddingLookUpFM_Gradient  one lookup consumed as rows, as reduce_sum_op(axes=1) and as
                                                   reduce_sum_op(mul_op(e, e), axes=1): the second-order term of the DeepFM models
                                                   (examples/ctr/models/deepfm_criteo.py:24-39)
-  ParameterServerCommunicateOp                    python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
+  EmbeddingLookUpFMSum / EmbeddingLookUpFMSum_Gradient  the same lookup when nothing consumes the rows: the pooled DeepFM
+                                                  (examples/ctr/models/emb_sum_deepfm_avazu.py); its gradient is applied by
+                                                  one fused launch (ops.sgd_apply_fm_bags)
+  ParameterServerCommunicateOp                   python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
   ParameterServerSparsePullOp                     python/hetu/gpu_ops/ParameterServerCommunicate.py:254-306
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
   Momentum / AdaGrad / Adam / AdamW sparse dispatch  python/hetu/gpu_links/OptimizerLink.py:37-100 (*_update_sparse: fused, and
@@ -268,9 +271,75 @@ class EmbeddingLookUpFM_Gradient:
         return ops.IndexedSlices(indices=index, values=values, dense_shape=self.embed_shape, push_indices=push)
 
 
+class EmbeddingLookUpFMSum(EmbeddingLookUp):
+    """embedding_lookup_op(embedding, index) consumed as reduce_sum_op(axes=1) and reduce_sum_op(mul_op(e, e), axes=1) ONLY, the
+    second-order term of the reference's pooled DeepFM (examples/ctr/models/emb_sum_deepfm_avazu.py, fae_deepfm_avazu.py):
+    S feeds the DNN and S*S, nothing consumes the per-occurrence rows.  compute(ids[B, F], sum_val[B, width], fm_val[B, width])
+    -- or ids[n] with offsets[B + 1] for ragged bags -- is ops.embedding_lookup_fm(want_rows=False): no [n, width] tensor.
+    A device table only: on the PS and cache tiers the rows an update is applied to may have changed since the lookup, and what
+    `e` means there is not decided."""
+
+    def forward_hook(self, config):
+        super().forward_hook(config)
+        if self.compute != self._compute_gpu:
+            raise ValueError("EmbeddingLookUpFMSum needs a device table (no PS, cache or prefetch tier): the pooled FM gradient "
+                             "is a function of the table row at the time of the update")
+        self.compute = self._compute_fm_sum
+
+    def _compute_fm_sum(self, ids, sum_val, fm_val, stream=None, offsets=None):
+        ops.embedding_lookup_fm(self.embedding.table, ids, offsets=offsets, sum_out=sum_val, fm_out=fm_val, want_rows=False,
+                                stream=stream)
+        return sum_val, fm_val
+
+
+class EmbeddingLookUpFMSum_Gradient:
+    """The gradient of EmbeddingLookUpFMSum: compute(sum_grad or None, fm_grad, sum, index) returns FM-POOLED IndexedSlices --
+    values is the gradient of S ([B, width], None when nothing consumed S), fm_grad the gradient of the FM output and fm_sum the
+    forward's S.  Nothing is computed here: the per-occurrence gradient (sum_grad[b] + fm_grad[b] * S[b]) - fm_grad[b] * e also
+    depends on the row e, which sgd_update_sparse's fused apply holds in registers (ops.sgd_apply_fm_bags)."""
+
+    def __init__(self, embed_shape):
+        self.embed_shape = embed_shape
+
+    def compute(self, sum_grad, fm_grad, sum, index, offsets=None, stream=None):
+        if isinstance(index, tuple):
+            raise TypeError("FM-pooled slices carry no push indices")
+        if offsets is None:
+            if index.dim() != 2:
+                raise ValueError("fixed bags need an index of shape [B, F]; give offsets for ragged bags")
+            return ops.IndexedSlices(indices=index, values=sum_grad, dense_shape=self.embed_shape, bag=index.shape[1],
+                                     fm_grad=fm_grad, fm_sum=sum)
+        return ops.IndexedSlices(indices=index, values=sum_grad, dense_shape=self.embed_shape,
+                                 bag_of=ops.bag_of(offsets, index.numel(), stream=stream), offsets=offsets, fm_grad=fm_grad,
+                                 fm_sum=sum)
+
+
+def _refuse_fm_pooled(name, grad):
+    """FM-pooled slices must never fall into a sum-pooled branch: it would silently drop the row term of the gradient."""
+    if getattr(grad, "fm_pooled", False):
+        raise ValueError("%s: FM-pooled slices (EmbeddingLookUpFMSum_Gradient) are taken by sgd_update_sparse on a device "
+                         "table only: the gradient of an occurrence depends on its table row" % name)
+
+
 def sgd_update_sparse(param, grad, lr, stream=None):
     """OptimizerOp's sparse SGD branch on a device table (OptimizerLink.py:23-33): no dedup, duplicates in
-    occurrence order.  Pooled slices (EmbeddingLookUpSum_Gradient) go to the bag apply: no expanded gradient is built."""
+    occurrence order.  Pooled slices (EmbeddingLookUpSum_Gradient) go to the bag apply: no expanded gradient is built.
+    FM-pooled slices (EmbeddingLookUpFMSum_Gradient) go to the fused FM apply: the one-call form for fixed bags, sort + finish +
+    ops.sgd_apply_fm_bags for ragged ones."""
+    if getattr(grad, "fm_pooled", False):
+        if param.table is None:
+            raise ValueError("sgd_update_sparse: FM-pooled slices need a device table")
+        width = param.table.shape[1]
+        g_sum = grad.values.reshape(-1, width).contiguous() if grad.values is not None else None
+        g_fm, fm_sum = grad.fm_grad.reshape(-1, width).contiguous(), grad.fm_sum.reshape(-1, width).contiguous()
+        if grad.bag is not None:
+            ops.sgd_sparse_update_fm_bags(param.table, grad.indices.reshape(-1, int(grad.bag)).contiguous(), g_sum, g_fm, fm_sum,
+                                          lr, stream=stream)
+        else:
+            ids = grad.indices.reshape(-1).contiguous()
+            plan = ops.IndexPlan(max(ids.numel(), 1), device=ids.device).sort(ids, stream).finish(stream)
+            ops.sgd_apply_fm_bags(param.table, plan, g_sum, g_fm, fm_sum, lr, bag_of=grad.bag_of, stream=stream)
+        return
     if getattr(grad, "pooled", False):
         width = param.table.shape[1]
         values = grad.values.reshape(-1, width).contiguous()
@@ -291,6 +360,7 @@ def sgd_update_sparse(param, grad, lr, stream=None):
 def _sparse_args(name, param, grad, states):
     """Shape checks shared by the *_update_sparse functions below (no native call is made before they pass).  Returns
     (table, width)."""
+    _refuse_fm_pooled(name, grad)
     table = param.table
     if table is None or table.dim() != 2:
         raise ValueError("%s: the parameter must hold a 2-D device table" % name)
@@ -511,7 +581,9 @@ class ParameterServerCommunicateOp:
         chain -- (Config.cache_fuse_bags), the call-by-call cache under its switch and the plain PS flavour
         (Config.ps_fuse_bags) are: slices
         pooled by the op's own bag size stay [B, width] -- on the PS flavour ragged slices that carry their offsets too --;
-        -lr is applied to those rows only, which is the same product for every occurrence of a bag."""
+        -lr is applied to those rows only, which is the same product for every occurrence of a bag.
+        FM-pooled slices are refused: the rows a push is applied to may have changed since the lookup."""
+        _refuse_fm_pooled("ParameterServerCommunicateOp", grad)
         if not getattr(grad, "pooled", False):
             return grad
         if self._bag is not None and grad.bag == self._bag:

@@ -594,6 +594,64 @@ def sgd_sparse_update_bags(table, ids, bag_grads, lr, offsets=None, stream=None)
     return table
 
 
+def _fm_pooled_args(table, g_sum, g_fm, sum):
+    """(nbags, width) of the three [B, width] tensors of an FM-pooled apply; g_sum may be None."""
+    _require(table, torch.float32, "table")
+    _require(g_fm, torch.float32, "g_fm")
+    _require(sum, torch.float32, "sum")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    width = table.shape[1]
+    if sum.dim() != 2 or sum.shape[1] != width or tuple(g_fm.shape) != tuple(sum.shape):
+        raise ValueError("sum and g_fm must both be [B, %d]" % width)
+    if g_sum is not None:
+        _require(g_sum, torch.float32, "g_sum")
+        if tuple(g_sum.shape) != tuple(sum.shape):
+            raise ValueError("g_sum must be shaped as sum")
+    for name, t in (("g_sum", g_sum), ("g_fm", g_fm), ("sum", sum)):
+        if t is not None and t.data_ptr() < table.data_ptr() + table.numel() * 4 and table.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError("%s must not alias the table" % name)
+    return sum.shape[0], width
+
+
+def sgd_apply_fm_bags(table, plan, g_sum, g_fm, sum, lr, bag=None, bag_of=None, stream=None):
+    """The backward of embedding_lookup_fm(want_rows=False) fused into the sparse SGD apply (ha_sgd_apply_fm_bags): for every
+    unique key, e = its row before the call and, per occurrence in order, row -= lr * ((g_sum[b] + g_fm[b] * sum[b]) - g_fm[b] * e)
+    with b the bag of the occurrence -- bit for bit embedding_lookup + fm_grad_rows on the expanded g_sum + sgd_apply, with no
+    [n, width] tensor.  plan: FINISHED (build(), or sort() + finish()).  g_sum: [B, width] or None (nothing consumed the sum);
+    g_fm, sum: [B, width], the gradient of fm and the forward's sum.  Give `bag` (fixed bags of that many ids) or `bag_of`
+    (int32 [n], from ops.bag_of).  The table must not have changed since the lookup that gave `sum`."""
+    nbags, width = _fm_pooled_args(table, g_sum, g_fm, sum)
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != plan.n:
+            raise ValueError("bag_of must have one entry per planned id")
+    elif bag < 1 or plan.n != nbags * bag:
+        raise ValueError("the plan must hold B * bag ids")
+    check(_lib.load().ha_sgd_apply_fm_bags(_ptr(table), table.shape[0], width, _ptr(plan.ws), plan.n,
+                                           _ptr(g_sum) if g_sum is not None else None, _ptr(g_fm), _ptr(sum),
+                                           int(bag) if bag is not None else 0, _ptr(bag_of) if bag_of is not None else None,
+                                           nbags, ctypes.c_float(lr), _stream_ptr(stream)), "ha_sgd_apply_fm_bags")
+    return table
+
+
+def sgd_sparse_update_fm_bags(table, ids, g_sum, g_fm, sum, lr, offsets=None, stream=None):
+    """One call: plan + sgd_apply_fm_bags.  ids / offsets as in embedding_lookup_fm; g_sum [B, width] or None, g_fm and sum
+    [B, width]."""
+    L = _lib.load()
+    nbags_t, width = _fm_pooled_args(table, g_sum, g_fm, sum)
+    n, bag, nbags = _bag_shape(ids, offsets)
+    if nbags_t != nbags:
+        raise ValueError("g_fm and sum must be [B, width]")
+    fn = _ids_fn(ids, L.ha_sgd_sparse_update_fm_bags_f32ids, L.ha_sgd_sparse_update_fm_bags_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), n, bag, _ptr(offsets) if offsets is not None else None, nbags,
+             _ptr(g_sum) if g_sum is not None else None, _ptr(g_fm), _ptr(sum), ctypes.c_float(lr), _stream_ptr(stream)),
+          "ha_sgd_sparse_update_fm_bags")
+    return table
+
+
 # ---- fused launches: two per training step --------------------------------------------------------
 def lookup_sort(table, ids, plan, out=None, stream=None):
     """Forward of one batch in ONE launch: out = table[ids] and plan.sort(ids)."""
@@ -1689,15 +1747,22 @@ class IndexedSlices:
     exactly what the reference computes with np.unique + DeduplicateIndexedSlices / cpu_deduplicate.
     """
 
-    def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None, offsets=None):
+    def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None, offsets=None,
+                 fm_grad=None, fm_sum=None):
         """bag / bag_of (optional): POOLED slices, the gradient of a sum-pooled lookup -- values is [B, width], one row per
         bag, and occurrence i of indices takes the row of its bag: i // bag (fixed bags of `bag` ids) or bag_of[i] (int32 [n],
         ragged bags).  offsets (optional, with bag_of): the int64 [B + 1] offsets bag_of was built from -- what the one-call
-        bag optimizers take (hetu_ops.*_update_sparse)."""
+        bag optimizers take (hetu_ops.*_update_sparse).
+        fm_grad / fm_sum (optional, together, with bag / bag_of): FM-POOLED slices, the gradient of an FM-pooled lookup whose
+        rows nothing consumed -- values is g_sum [B, width] or None, fm_grad [B, width] the gradient of the FM output and
+        fm_sum [B, width] the forward's sum; the gradient of an occurrence also depends on its table row
+        (ops.sgd_apply_fm_bags), so only the SGD update takes them."""
         if bag is not None and bag_of is not None:
             raise ValueError("give at most one of bag and bag_of")
         if offsets is not None and bag_of is None:
             raise ValueError("offsets come with bag_of (ragged bags)")
+        self._check_fm(fm_grad, fm_sum, bag, bag_of)
+        self.fm_grad, self.fm_sum = fm_grad, fm_sum
         self.offsets = offsets
         self.indices = indices
         self.values = values
@@ -1706,12 +1771,30 @@ class IndexedSlices:
         self.bag, self.bag_of = bag, bag_of
         self.deduplicated = False
 
+    @staticmethod
+    def _check_fm(fm_grad, fm_sum, bag, bag_of):
+        if (fm_grad is None) != (fm_sum is None):
+            raise ValueError("fm_grad and fm_sum come together")
+        if fm_grad is not None and bag is None and bag_of is None:
+            raise ValueError("fm_grad / fm_sum come with bag or bag_of (FM-pooled slices)")
+
     @property
     def pooled(self):
         return self.bag is not None or self.bag_of is not None
 
+    @property
+    def fm_pooled(self):
+        """FM-pooled slices: the gradient of an occurrence is (values[b] + fm_grad[b] * fm_sum[b]) - fm_grad[b] * its row."""
+        return self.fm_grad is not None
+
+    def _no_fm_pooled(self, what):
+        if self.fm_pooled:
+            raise ValueError("FM-pooled IndexedSlices (fm_grad / fm_sum) %s: the gradient of an occurrence depends on its "
+                             "table row" % what)
+
     def expanded_values(self, stream=None):
         """Per-occurrence values [n, width] of pooled slices (every occurrence a copy of its bag's row)."""
+        self._no_fm_pooled("have no expanded values")
         width = self.values.shape[-1]
         vals = self.values.reshape(-1, width).contiguous()
         if not self.pooled:
@@ -1730,10 +1813,13 @@ class IndexedSlices:
     def get_sparse_shape(self):
         return tuple(self.values.shape)
 
-    def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None, offsets=None):
+    def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None, offsets=None, fm_grad=None,
+               fm_sum=None):
+        self._check_fm(fm_grad, fm_sum, bag, bag_of)
         self.indices = indices
         self.push_indices = push_indices
         self.bag, self.bag_of, self.offsets = bag, bag_of, offsets
+        self.fm_grad, self.fm_sum = fm_grad, fm_sum
         self.values = values
         if self.dense_shape is not None:
             assert tuple(self.dense_shape) == tuple(dense_shape)
@@ -1742,6 +1828,7 @@ class IndexedSlices:
         self.deduplicated = False
 
     def deduplicate(self, stream=None):
+        self._no_fm_pooled("cannot be deduplicated")
         if self.pooled:
             raise ValueError("pooled IndexedSlices (bag / bag_of) cannot be deduplicated: values holds one row per bag")
         ids = self.indices.reshape(-1)
@@ -1761,6 +1848,7 @@ class IndexedSlices:
         return self
 
     def to_dense(self, stream=None):
+        self._no_fm_pooled("have no dense form")
         if self.pooled:
             raise ValueError("pooled IndexedSlices (bag / bag_of) have no dense form: values holds one row per bag")
         dense = torch.zeros(tuple(self.get_dense_shape()), dtype=torch.float32, device=self.values.device)

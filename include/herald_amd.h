@@ -1460,6 +1460,40 @@ int ha_gather_fm_u64ids(const float *table, int64_t rows, int64_t width, const u
  * width % 4 == 0 with every pointer 16-byte aligned takes 16-byte accesses.  Checked before any device access. */
 int ha_fm_grad_rows(const float *g_rows, const float *emb_rows, const float *sum, const float *g_fm, int64_t n,
                     int64_t width, int64_t bag, const int32_t *bag_of, int64_t nbags, float *out, ha_stream_t stream);
+/* The backward of ha_gather_fm_* when nothing consumed the rows (out_rows == NULL: the pooled DeepFM,
+ * examples/ctr/models/emb_sum_deepfm_avazu.py, where the lookup is consumed as S and as 0.5 * (S*S - Q) only), fused into the
+ * sparse SGD apply: ONE launch that reads every unique row once and writes it once; no [n, width] tensor exists.
+ * plan_ws: a FINISHED plan of the n ids (ha_plan_build_*, or ha_plan_sort_* + ha_plan_finish): what ha_sgd_apply_finished
+ * takes.  g_fm, sum [nbags, width]: the gradient of out_fm and the forward's out_sum.  g_sum [nbags, width]: the gradient of
+ * out_sum, or NULL when nothing consumed the sum.  Bags as ha_sgd_apply_bags: exactly one of bag >= 1 (fixed bags,
+ * n == nbags * bag, b = i / bag in registers) and bag_of (int32[n] from ha_bag_of, bag == 0).
+ * For every unique key k < rows with occurrences i0 < i1 < ..., let e = table[k,:] AS IT IS BEFORE THE CALL and acc = e; for
+ * each occurrence in order, with b its bag and every operation rounded on its own:
+ *   a   = fl(g_fm[b] * sum[b]);   with g_sum: a = fl(g_sum[b] + a)
+ *   g   = fl(a - fl(g_fm[b] * e))
+ *   acc = fl(acc - fl(lr * g))
+ * then table[k,:] = acc.  Keys >= rows are ignored, rows that no id names are not touched.  Any width >= 1; width % 4 == 0
+ * with every pointer 16-byte aligned takes 16-byte accesses.  None of g_sum, g_fm, sum may alias table.  n == 0 is not an
+ * error.  Every argument check precedes any device access.
+ * Equivalence: bit for bit E = ha_gather_*(table, ids), G = ha_fm_grad_rows(g_sum expanded to [n, width], E, sum, g_fm),
+ * ha_sgd_apply(table, plan, G, lr) -- the project's fixed order of the three adjoints, unchanged.  That holds when the table
+ * has not changed between the lookup that produced `sum` and this call (true of a table in HBM that only its own step
+ * updates): e is the row now, not the row the lookup saw.
+ * Tolerance mode 1 or 2 (ha_set_tolerance_mode): the entry points run exactly that composed sequence through the library's
+ * per-stream scratch (rows and gradient, 2 * n * width floats) and are whatever ha_sgd_apply_finished is in that mode; the
+ * fused kernel serves mode 0, the default, only.  plan_ws, bag_of and the three tensors must then be the caller's own
+ * allocations, never pointers into that scratch (see ha_dedup_reduce_bags). */
+int ha_sgd_apply_fm_bags(float *table, int64_t rows, int64_t width, void *plan_ws, int64_t n, const float *g_sum,
+                         const float *g_fm, const float *sum, int64_t bag, const int32_t *bag_of, int64_t nbags, float lr,
+                         ha_stream_t stream);
+/* One call: plan (sort + finish) (+ ha_bag_of) + ha_sgd_apply_fm_bags, on an internal per-stream workspace.  bag / offsets
+ * as ha_sgd_sparse_update_bags_* takes them: exactly one of bag >= 1 (n == nbags * bag) and offsets (int64[nbags + 1]). */
+int ha_sgd_sparse_update_fm_bags_f32ids(float *table, int64_t rows, int64_t width, const float *ids, int64_t n, int64_t bag,
+                                        const int64_t *offsets, int64_t nbags, const float *g_sum, const float *g_fm,
+                                        const float *sum, float lr, ha_stream_t stream);
+int ha_sgd_sparse_update_fm_bags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
+                                        const int64_t *offsets, int64_t nbags, const float *g_sum, const float *g_fm,
+                                        const float *sum, float lr, ha_stream_t stream);
 /* Measurement aid (tools/bag_bench.py): column-slice width of ha_gather_sum_*'s 16-byte path, 64 / 128 / 256 floats per
  * wave; 0 = chosen from the batch (the default).  Process-wide; results do not depend on it. */
 int ha_debug_bag_slice(int floats);
