@@ -56,6 +56,12 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      emb_sum_dfm_avazu): the second-order lookup is consumed only as S (the DNN's input and S*S) and Q, so the
                      lookup writes no rows (ha_gather_fm_* with out_rows NULL) and its whole backward is ONE fused apply
                      (ha_sgd_sparse_update_fm_bags_*): no [batch * 26, d] tensor in the step.  --embedding hbm, --optimizer sgd.
+  --model fae_wdl    the FAE Wide & Deep (examples/ctr/models/fae_wdl_criteo.py; also fae_wdl_criteo): the --fae-hot-rate most
+                     frequent ids of the run are served by a small dense table that trains with the tower (its half of a sample's
+                     sum: torch's embedding_bag with per-sample weights), every other id by the main table through the WEIGHTED
+                     sum-pooled lookup (ha_gather_wsum_*: the slot of a hot id is the padding id 0 with weight 0) and, with
+                     --optimizer sgd, the fused weighted apply (ha_sgd_sparse_update_wbags_*: the dead slots leave the plan as
+                     one out-of-range key); the other optimizers take the weighted gradient expanded.  --embedding hbm only.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -228,13 +234,32 @@ class FMSumLookup(torch.autograd.Function):
 
 POOLED_MODELS = ("emb_sum_wdl",)
 FM_MODELS = ("deepfm", "emb_sum_deepfm")
-MODEL_ALIASES = {"emb_sum_deepfm_avazu": "emb_sum_deepfm", "emb_sum_dfm_avazu": "emb_sum_deepfm"}
+FAE_MODELS = ("fae_wdl",)
+MODEL_ALIASES = {"emb_sum_deepfm_avazu": "emb_sum_deepfm", "emb_sum_dfm_avazu": "emb_sum_deepfm", "fae_wdl_criteo": "fae_wdl"}
 OPTIMIZERS = ("sgd", "momentum", "nesterov", "adagrad", "adam", "adamw")
 
 
 def make_tower(model, width, seed=0):
     return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower, "deepfm": FMTower,
-            "emb_sum_deepfm": SumFMTower}[model](width, seed)
+            "emb_sum_deepfm": SumFMTower, "fae_wdl": SumTower}[model](width, seed)
+
+
+def fae_hot_ids(batches, rows, rate):
+    """The hot list of an FAE run, on the host: the int(rate * rows) most frequent ids of the run's batches, most frequent first,
+    ties to the smaller id (int64 [num_hot])."""
+    counts = np.bincount(np.concatenate([b[0].reshape(-1) for b in batches]).astype(np.int64), minlength=rows)
+    order = np.lexsort((np.arange(rows), -counts))
+    return order[:int(rate * rows)]
+
+
+def fae_split(ids, hot):
+    """A batch's ids [B, 26] split by the hot list: hot_rank int64 (the 1-based rank of a hot id, 0 if the id is cold), cold_ids
+    float32 (the id if cold, else the padding id 0) and cold_mask float32 (1.0 where the id is cold)."""
+    rank_of = np.zeros(max(int(ids.max()) + 1, int(hot.max(initial=0)) + 1), dtype=np.int64)
+    rank_of[hot] = np.arange(1, hot.size + 1)
+    hot_rank = rank_of[ids.astype(np.int64)]
+    cold = hot_rank == 0
+    return hot_rank, np.where(cold, ids, np.float32(0)).astype(np.float32), cold.astype(np.float32)
 
 
 def make_samples(nsamples, rows, seed=0):
@@ -407,7 +432,7 @@ def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
-          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False, first_order_init=None):
+          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False, first_order_init=None, fae_hot_rate=0.01):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -428,7 +453,12 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     tower keeps SGD.  opt_fuse_bags=False: the reference's own sequence for it (expanded gradient, deduplicate, the symbol) --
     the same bits.
     model="deepfm" (--model deepfm): DeepFM, --embedding hbm with --optimizer sgd only (train_deepfm); first_order_init: its
-    first-order table [rows, 1] (default: N(0, 0.01) from seed + 2), table_init the second-order one."""
+    first-order table [rows, 1] (default: N(0, 0.01) from seed + 2), table_init the second-order one.
+    model="fae_wdl" (--model fae_wdl), --embedding hbm only: the int(fae_hot_rate * rows) most frequent ids of the run's batches
+    are hot (fae_hot_ids).  The hot table [num_hot, width] is a torch parameter, initialised from the main table's rows at the
+    hot ids and trained with the tower; its half of a sample's sum is embedding_bag with per-sample weights 1 - cold_mask.  The
+    cold half is EmbeddingLookUpWeightedSum on the main table over (cold_ids, cold_mask), its gradient weighted pooled slices:
+    --optimizer sgd applies them fused, the others expanded.  The returned parameter carries `hot_table` and `hot_ids`."""
     if model in FM_MODELS:
         if embedding != "hbm" or optimizer != "sgd":
             raise ValueError("%s runs with --embedding hbm and --optimizer sgd only: its FM-pooled lookup is not part of the "
@@ -437,6 +467,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
         return train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every, model)
     dev = torch.device(device)
     pooled = model in POOLED_MODELS
+    fae = model in FAE_MODELS
+    if fae and embedding != "hbm":
+        raise ValueError("%s runs with --embedding hbm only: the weighted sum-pooled lookup has no form on the step engines and "
+                         "no pooled form on the PS or the cache tiers (got --embedding %s)" % (model, embedding))
     if optimizer not in OPTIMIZERS:
         raise ValueError("optimizer must be one of %s, got %r" % (", ".join(OPTIMIZERS), optimizer))
     if optimizer != "sgd" and embedding != "hbm":
@@ -483,7 +517,17 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                                      bag=NFIELD if pooled and embedding in ("cache", "ps") else None)
         barrier = dist.barrier if world > 1 else (lambda: None)
         comm.forward_hook(config, first_ids=ids_of(0), barrier=barrier)
-    if pooled:
+    hot_table = None
+    if fae:
+        # the hot list from the run's batches, every batch split by it; the hot table starts as the main table's hot rows
+        hot = fae_hot_ids(batches, rows, fae_hot_rate)
+        splits = [tuple(torch.from_numpy(a).to(dev) for a in fae_split(b[0], hot)) for b in batches]
+        param.hot_ids = torch.from_numpy(hot).to(dev)
+        param.hot_table = hot_table = torch.nn.Parameter(param.table[param.hot_ids].clone())
+        opt.add_param_group({"params": [hot_table]})
+        lookup = hetu_ops.EmbeddingLookUpWeightedSum(param)
+        lookup_grad = hetu_ops.EmbeddingLookUpWeightedSum_Gradient(param.shape)
+    elif pooled:
         # embedding_lookup_op + reduce_sum_op(axes=1) as one operator: the fused kernel on a device table, the same ordered sum
         # over the delivered rows on the ps / cache paths; its gradient stays [batch, width] (pooled IndexedSlices)
         lookup = hetu_ops.EmbeddingLookUpSum(param)
@@ -550,11 +594,21 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
             emb = pipe_out.detach().clone()                        # written by the previous step's launch
         elif fused is not None:
             emb = fused["outs"][k % 2].detach().clone()            # looked up by the previous step's launch
+        elif fae:
+            hot_rank, cold_ids, cold_mask = splits[k % len(splits)]
+            emb = torch.empty((batch, width), dtype=torch.float32, device=dev)
+            lookup.compute(cold_ids, cold_mask, emb)               # embedding_lookup_op, mul_op by the mask, reduce_sum_op(axes=1)
         else:
             emb = torch.empty((batch, width) if pooled else (batch, NFIELD, width), dtype=torch.float32, device=dev)
             lookup.compute(ids, emb)                               # embedding_lookup_op (+ reduce_sum_op(axes=1))
         emb.requires_grad_(True)
-        pred = tower(dense, emb.reshape(batch, -1))
+        if fae and hot_table.shape[0] > 0:
+            # the hot half of the sum: a cold slot reads hot row 0 with weight 0
+            hot_sum = torch.nn.functional.embedding_bag((hot_rank - 1).clamp_(min=0), hot_table, per_sample_weights=1 - cold_mask,
+                                                        mode="sum")
+            pred = tower(dense, emb + hot_sum)
+        else:
+            pred = tower(dense, emb.reshape(batch, -1))
         loss = torch.nn.functional.binary_cross_entropy(pred, label)
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -563,7 +617,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                 allreduce(p_.grad)
                 p_.grad.div_(world)
         opt.step()
-        grad = lookup_grad.compute(emb.grad, ids)                  # IndexedSlices(indices, values)
+        if fae:
+            grad = lookup_grad.compute(emb.grad, cold_ids, cold_mask)      # weighted pooled IndexedSlices
+        else:
+            grad = lookup_grad.compute(emb.grad, ids)              # IndexedSlices(indices, values)
         if pipe is not None:
             # sparse SGD of this batch, rows of the next one, plan finish of batch k+2, sort of batch k+3: one launch
             pipe_out = pipe.step(grad.values.reshape(-1, width).contiguous(),
@@ -622,8 +679,10 @@ def main():
     # table with one launch per step, "queue" = the work-queue step with lookahead, ...).
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo | deepfm_criteo | "
-                                                   "emb_sum_deepfm_avazu | emb_sum_dfm_avazu (the reference's names) or "
-                                                   "wdl | dcn | emb_sum_wdl | deepfm | emb_sum_deepfm")
+                                                   "emb_sum_deepfm_avazu | emb_sum_dfm_avazu | fae_wdl_criteo (the reference's "
+                                                   "names) or wdl | dcn | emb_sum_wdl | deepfm | emb_sum_deepfm | fae_wdl")
+    ap.add_argument("--fae-hot-rate", type=float, default=0.01,
+                    help="--model fae_wdl: the share of the table's rows, most frequent ids first, served by the hot table")
     ap.add_argument("-b", "--batch-size", "--batch", dest="batch", type=int, default=256)
     ap.add_argument("-e", "--embedding-size", "--width", dest="width", type=int, default=128)
     ap.add_argument("-r", "--cache-limit-ratio", type=float, default=0.1,
@@ -664,9 +723,9 @@ def main():
     ap.add_argument("--local-shared", action="store_true", help="--laia with the TopkScheduler + shared-memory rings")
     args = ap.parse_args()
     model = args.model[:-len("_criteo")] if args.model.endswith("_criteo") else MODEL_ALIASES.get(args.model, args.model)
-    if model not in ("wdl", "dcn") + POOLED_MODELS + FM_MODELS:
+    if model not in ("wdl", "dcn") + POOLED_MODELS + FM_MODELS + FAE_MODELS:
         ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, deepfm_criteo, emb_sum_deepfm_avazu, "
-                 "emb_sum_dfm_avazu, wdl, dcn, emb_sum_wdl, deepfm or emb_sum_deepfm")
+                 "emb_sum_dfm_avazu, fae_wdl_criteo, wdl, dcn, emb_sum_wdl, deepfm, emb_sum_deepfm or fae_wdl")
     args.model = model
     if model in POOLED_MODELS and (args.laia or args.embedding in ("step", "step3", "queue")):
         ap.error("--model %s pools its embeddings: use --embedding hbm (the fused kernel), ps or cache; the step engines "
@@ -684,6 +743,8 @@ def main():
         ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
     if model in FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
         ap.error("--model %s runs with --embedding hbm and --optimizer sgd only" % model)
+    if model in FAE_MODELS and (args.laia or args.embedding != "hbm"):
+        ap.error("--model %s runs with --embedding hbm only" % model)
     if args.nepoch > 0:
         args.steps *= args.nepoch
     cache_limit = max(int(args.cache_limit_ratio * args.rows), args.batch * NFIELD)
@@ -701,7 +762,8 @@ def main():
                        args.bound, cache_limit=cache_limit, device="cuda:%d" % local_rank,
                        log_every=max(1, args.steps // 10), model=args.model, bsp=args.bsp if comm is not None else 0,
                        cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer,
-                       ps_fuse_bags=not args.no_ps_fuse_bags, cache_fuse_bag_calls=args.cache_fuse_bag_calls)[0]
+                       ps_fuse_bags=not args.no_ps_fuse_bags, cache_fuse_bag_calls=args.cache_fuse_bag_calls,
+                       fae_hot_rate=args.fae_hot_rate)[0]
     if local_rank == 0:
         print("first 10 steps: loss %.5f   last 10 steps: loss %.5f" % (np.mean(losses[:10]), np.mean(losses[-10:])))
 

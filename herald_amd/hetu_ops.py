@@ -11,6 +11,11 @@ Mirrors (paths relative to /root/reference):
   EmbeddingLookUpFMSum / EmbeddingLookUpFMSum_Gradient  the same lookup when nothing consumes the rows: the pooled DeepFM
                                                   (examples/ctr/models/emb_sum_deepfm_avazu.py); its gradient is applied by
                                                   one fused launch (ops.sgd_apply_fm_bags)
+  EmbeddingLookUpWeightedSum / EmbeddingLookUpWeightedSum_Gradient  the lookup followed by mul_op with a per-occurrence weight
+                                                  and reduce_sum_op(axes=1): the FAE models (examples/ctr/models/
+                                                  fae_wdl_criteo.py:19-31); its gradient is weighted pooled slices, applied by
+                                                  one fused launch chain (ops.sgd_sparse_update_wbags) or expanded first
+                                                  (unweighted_slices) for every consumer without a weighted form
   ParameterServerCommunicateOp                   python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
   ParameterServerSparsePullOp                     python/hetu/gpu_ops/ParameterServerCommunicate.py:254-306
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
@@ -314,6 +319,72 @@ class EmbeddingLookUpFMSum_Gradient:
                                  fm_sum=sum)
 
 
+class EmbeddingLookUpWeightedSum(EmbeddingLookUp):
+    """embedding_lookup_op(embedding, index), mul_op by a per-occurrence weight and reduce_sum_op(axes=1): the embedding path of
+    the reference's FAE models (examples/ctr/models/fae_wdl_criteo.py:19-31), where the weight is the 0/1 mask of the cold ids.
+    compute(ids[B, F], weights[B, F], output_val[B, width]) -- or ids[n], weights[n] with offsets[B + 1] for ragged bags.  With a
+    device table it is the fused kernel (ops.embedding_lookup_wsum): a dead occurrence (zero weight, or id >= rows) takes no
+    part.  On the PS, cache and prefetched paths the per-occurrence rows arrive as EmbeddingLookUp delivers them and the same
+    kernel sums them out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Those tiers have no
+    pooled weighted form: a communicate op that pulls POOLED rows (bag=) cannot serve this operator and is refused."""
+
+    def forward_hook(self, config):
+        super().forward_hook(config)
+        self._rows_compute = self.compute
+        self._fused = self._rows_compute == self._compute_gpu
+        self._pos = None
+        self.compute = self._compute_wsum
+
+    def _compute_wsum(self, ids, weights, output_val, stream=None, offsets=None):
+        if self._fused:
+            return ops.embedding_lookup_wsum(self.embedding.table, ids, weights, offsets=offsets, out=output_val, stream=stream)
+        if getattr(self.config, "ps_pooled", {}).get(self.embedding) is not None:
+            raise ValueError("EmbeddingLookUpWeightedSum: the communicate op pulls pooled rows (bag=%d), which carry no weights; "
+                             "build it without bag=" % self.config.ps_pooled[self.embedding])
+        n, width = ids.numel(), self.embedding.shape[1]
+        if self._pos is None or self._pos.numel() < n or self._pos.device != output_val.device:
+            self._pos = torch.arange(max(n, 1), dtype=torch.int64, device=output_val.device)
+        rows = torch.empty((n, width), dtype=torch.float32, device=output_val.device)
+        self._rows_compute(ids, rows.view(tuple(ids.shape) + (width,)), stream)
+        # (a row the store delivered as zeros for an id beyond the table is added as zeros times its weight: +0 or -0 into a
+        # chain that starts at +0, which leaves every sum as it is)
+        return ops.embedding_lookup_wsum(rows, self._pos[:n].view(ids.shape), weights, offsets=offsets, out=output_val,
+                                         stream=stream)
+
+
+class EmbeddingLookUpWeightedSum_Gradient:
+    """The gradient of EmbeddingLookUpWeightedSum: compute(vectors[B, width], index, weights) returns WEIGHTED POOLED
+    IndexedSlices -- values stay [B, width], the gradient of occurrence i is weights[i] * values[its bag].  sgd_update_sparse
+    applies them fused (ops.sgd_apply_wbags); every other consumer expands them first (unweighted_slices)."""
+
+    def __init__(self, embed_shape, enable_push_index=False):
+        self.embed_shape, self.enable_push_index = embed_shape, enable_push_index
+
+    def compute(self, vectors, index, weights, offsets=None):
+        push = None
+        if isinstance(index, tuple):
+            index, push = index[0], (index[1] if self.enable_push_index else None)
+        elif self.enable_push_index:
+            raise TypeError
+        if offsets is None:
+            if index.dim() != 2:
+                raise ValueError("fixed bags need an index of shape [B, F]; give offsets for ragged bags")
+            return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
+                                     bag=index.shape[1], weights=weights)
+        return ops.IndexedSlices(indices=index, values=vectors, dense_shape=self.embed_shape, push_indices=push,
+                                 bag_of=ops.bag_of(offsets, index.numel()), offsets=offsets, weights=weights)
+
+
+def unweighted_slices(grad, stream=None):
+    """Weighted pooled slices as ordinary UNPOOLED ones (values [n, width] = ops.wbag_grad_rows), anything else as it is.  The
+    one door every consumer without a weighted form goes through -- the other optimizers, the communicate op's pushes, the
+    fuse_bags branches -- so that a weight can never be silently dropped by a sum-pooled branch."""
+    if not getattr(grad, "weighted", False):
+        return grad
+    return ops.IndexedSlices(indices=grad.indices, values=grad.expanded_values(stream), dense_shape=grad.dense_shape,
+                             push_indices=grad.push_indices)
+
+
 def _refuse_fm_pooled(name, grad):
     """FM-pooled slices must never fall into a sum-pooled branch: it would silently drop the row term of the gradient."""
     if getattr(grad, "fm_pooled", False):
@@ -339,6 +410,28 @@ def sgd_update_sparse(param, grad, lr, stream=None):
             ids = grad.indices.reshape(-1).contiguous()
             plan = ops.IndexPlan(max(ids.numel(), 1), device=ids.device).sort(ids, stream).finish(stream)
             ops.sgd_apply_fm_bags(param.table, plan, g_sum, g_fm, fm_sum, lr, bag_of=grad.bag_of, stream=stream)
+        return
+    if getattr(grad, "weighted", False):
+        # weighted pooled slices (EmbeddingLookUpWeightedSum_Gradient): the fused weighted apply over masked keys -- the one-call
+        # form for fixed bags; mask + sort + finish + ops.sgd_apply_wbags for ragged ones
+        if param.table is None:
+            raise ValueError("sgd_update_sparse: weighted pooled slices need a device table")
+        table = param.table
+        width = table.shape[1]
+        values = grad.values.reshape(-1, width).contiguous()
+        weights = grad.weights.reshape(-1).contiguous()
+        if grad.bag is not None:
+            ops.sgd_sparse_update_wbags(table, grad.indices.reshape(-1, int(grad.bag)).contiguous(), values, weights, lr,
+                                        stream=stream)
+        else:
+            ids = grad.indices.reshape(-1).contiguous()
+            keys = ids.to(torch.int64)
+            if ids.dtype == torch.float32:      # (as the kernels read float32 ids: toward zero, a negative one is row 0)
+                keys = keys.clamp_(min=0)
+            keys = torch.where((weights != 0) & (keys >= 0) & (keys < table.shape[0]), keys,
+                               torch.full_like(keys, table.shape[0]))
+            plan = ops.IndexPlan(max(keys.numel(), 1), device=keys.device).sort(keys, stream, key_limit=table.shape[0])
+            ops.sgd_apply_wbags(table, plan.finish(stream), values, weights, lr, bag_of=grad.bag_of, stream=stream)
         return
     if getattr(grad, "pooled", False):
         width = param.table.shape[1]
@@ -412,7 +505,8 @@ def _bag_call_args(name, grad, width):
 def momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream=None, fuse_bags=True):
     """momentum_update's sparse branch (OptimizerLink.py:37-49): MomentumOptimizerSparseUpdate WITHOUT deduplication.
     Pooled slices go to ops.momentum_sparse_update_bags -- no expanded gradient is built; fuse_bags=False runs the reference's
-    sequence (expanded_values, then the symbol): the same bits."""
+    sequence (expanded_values, then the symbol): the same bits.  Weighted pooled slices are expanded first (unweighted_slices)."""
+    grad = unweighted_slices(grad, stream)
     table, width = _sparse_args("momentum_update_sparse", param, grad, [("velocity", velocity)])
     if fuse_bags and getattr(grad, "pooled", False):
         ids, offsets, values = _bag_call_args("momentum_update_sparse", grad, width)
@@ -425,6 +519,7 @@ def momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream
 
 def _fused_update_sparse(name, kind, symbol, param, grad, state1, state2, hyper, scalars, stream, fuse_bags):
     states = [("the first state", state1)] + ([("the second state", state2)] if kind != "adagrad" else [])
+    grad = unweighted_slices(grad, stream)      # weighted pooled slices: expanded first, whatever fuse_bags says
     table, width = _sparse_args(name, param, grad, states)
     if not fuse_bags:        # the reference: deduplicate (on the expanded gradient), then the symbol on the reduced slices
         ids, values = _reference_slices(grad, width, True, stream)
@@ -582,8 +677,10 @@ class ParameterServerCommunicateOp:
         (Config.ps_fuse_bags) are: slices
         pooled by the op's own bag size stay [B, width] -- on the PS flavour ragged slices that carry their offsets too --;
         -lr is applied to those rows only, which is the same product for every occurrence of a bag.
-        FM-pooled slices are refused: the rows a push is applied to may have changed since the lookup."""
+        FM-pooled slices are refused: the rows a push is applied to may have changed since the lookup.  Weighted pooled slices
+        (EmbeddingLookUpWeightedSum_Gradient) are expanded first on every store and schedule: no tier has a pooled weighted form."""
         _refuse_fm_pooled("ParameterServerCommunicateOp", grad)
+        grad = unweighted_slices(grad)
         if not getattr(grad, "pooled", False):
             return grad
         if self._bag is not None and grad.bag == self._bag:

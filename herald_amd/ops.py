@@ -652,6 +652,117 @@ def sgd_sparse_update_fm_bags(table, ids, g_sum, g_fm, sum, lr, offsets=None, st
     return table
 
 
+# ---- weighted bags (the masked sum-pooled lookup of the FAE models, csrc/wbag.hip) ---------------------------------------
+def _weights_of(weights, n):
+    _require(weights, torch.float32, "weights")
+    if weights.numel() != n:
+        raise ValueError("weights must have one entry per occurrence (%d), got %d" % (n, weights.numel()))
+    return weights
+
+
+def embedding_lookup_wsum(table, ids, weights, offsets=None, out=None, stream=None):
+    """Weighted sum-pooled lookup (ha_gather_wsum_*): out[b, :] = the position-ordered chain acc = fl(acc + fl(w_j * r_j)) from
+    +0 over the LIVE occurrences of bag b -- weight not zero and id < rows; a dead occurrence takes no part, whatever its row
+    holds.  ids / offsets as in embedding_lookup_sum, weights float32 with one entry per id.  All weights 1: embedding_lookup_sum
+    bit for bit.  Returns out [B, width]."""
+    L = _lib.load()
+    _require(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    _weights_of(weights, n)
+    width = table.shape[1]
+    if out is None:
+        out = torch.empty((nbags, width), dtype=torch.float32, device=table.device)
+    _require(out, torch.float32, "out")
+    if out.numel() != nbags * width:
+        raise ValueError("out has the wrong size")
+    fn = _ids_fn(ids, L.ha_gather_wsum_f32ids, L.ha_gather_wsum_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), _ptr(weights), n, bag,
+             _ptr(offsets) if offsets is not None else None, nbags, _ptr(out), _stream_ptr(stream)), "ha_gather_wsum")
+    return out
+
+
+def wbag_grad_rows(bag_grads, weights, bag=None, bag_of=None, out=None, stream=None):
+    """The per-occurrence gradient of embedding_lookup_wsum (ha_wbag_grad_rows): out[i, :] = fl(w_i * bag_grads[bag of i, :]),
+    exactly +0 where w_i is zero.  bag_grads [B, width]; give `bag` (fixed bags of that many ids) or `bag_of` (int32 [n], from
+    ops.bag_of).  Returns out [n, width], an ordinary unpooled gradient."""
+    _require(bag_grads, torch.float32, "bag_grads")
+    if bag_grads.dim() != 2:
+        raise ValueError("bag_grads must be [B, width]")
+    nbags, width = bag_grads.shape
+    n = weights.numel()
+    _weights_of(weights, n)
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != n:
+            raise ValueError("bag_of must have one entry per occurrence")
+    elif bag < 1 or n != nbags * bag:
+        raise ValueError("weights must hold B * bag entries")
+    if out is None:
+        out = torch.empty((n, width), dtype=torch.float32, device=bag_grads.device)
+    _require(out, torch.float32, "out")
+    if out.numel() != n * width:
+        raise ValueError("out has the wrong size")
+    check(_lib.load().ha_wbag_grad_rows(_ptr(bag_grads), _ptr(weights), n, width, int(bag) if bag is not None else 0,
+                                        _ptr(bag_of) if bag_of is not None else None, nbags, _ptr(out), _stream_ptr(stream)),
+          "ha_wbag_grad_rows")
+    return out
+
+
+def _wbag_apply_args(table, bag_grads, weights):
+    _require(table, torch.float32, "table")
+    _require(bag_grads, torch.float32, "bag_grads")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    if bag_grads.dim() != 2 or bag_grads.shape[1] != table.shape[1]:
+        raise ValueError("bag_grads must be [B, %d]" % table.shape[1])
+    for name, t in (("bag_grads", bag_grads), ("weights", weights)):
+        if t.data_ptr() < table.data_ptr() + table.numel() * 4 and table.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError("%s must not alias the table" % name)
+    return bag_grads.shape[0], table.shape[1]
+
+
+def sgd_apply_wbags(table, plan, bag_grads, weights, lr, bag=None, bag_of=None, stream=None):
+    """The backward of embedding_lookup_wsum fused into the sparse SGD apply (ha_sgd_apply_wbags): for every key, over its live
+    occurrences in order, row -= lr * (w_i * bag_grads[bag of i]) -- three roundings, no [n, width] tensor; a key without live
+    occurrence keeps its bits.  plan: FINISHED (build(), or sort() + finish()), of the ids or of masked keys (a key >= rows for a
+    dead occurrence): the same table either way.  Give `bag` or `bag_of` as in sgd_apply_bags."""
+    nbags, width = _wbag_apply_args(table, bag_grads, weights)
+    _weights_of(weights, plan.n)
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != plan.n:
+            raise ValueError("bag_of must have one entry per planned id")
+    elif bag < 1 or plan.n != nbags * bag:
+        raise ValueError("the plan must hold B * bag ids")
+    check(_lib.load().ha_sgd_apply_wbags(_ptr(table), table.shape[0], width, _ptr(plan.ws), plan.n, _ptr(bag_grads),
+                                         _ptr(weights), int(bag) if bag is not None else 0,
+                                         _ptr(bag_of) if bag_of is not None else None, nbags, ctypes.c_float(lr),
+                                         _stream_ptr(stream)), "ha_sgd_apply_wbags")
+    return table
+
+
+def sgd_sparse_update_wbags(table, ids, bag_grads, weights, lr, offsets=None, stream=None):
+    """One call: masked keys + plan + sgd_apply_wbags (ha_sgd_sparse_update_wbags_*).  ids / offsets as in
+    embedding_lookup_wsum, bag_grads [B, width].  The dead occurrences leave the plan as one out-of-range key."""
+    L = _lib.load()
+    nbags_t, width = _wbag_apply_args(table, bag_grads, weights)
+    n, bag, nbags = _bag_shape(ids, offsets)
+    _weights_of(weights, n)
+    if nbags_t != nbags:
+        raise ValueError("bag_grads must be [B, width]")
+    fn = _ids_fn(ids, L.ha_sgd_sparse_update_wbags_f32ids, L.ha_sgd_sparse_update_wbags_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), _ptr(weights), n, _ptr(bag_grads), bag,
+             _ptr(offsets) if offsets is not None else None, nbags, ctypes.c_float(lr), _stream_ptr(stream)),
+          "ha_sgd_sparse_update_wbags")
+    return table
+
+
 # ---- fused launches: two per training step --------------------------------------------------------
 def lookup_sort(table, ids, plan, out=None, stream=None):
     """Forward of one batch in ONE launch: out = table[ids] and plan.sort(ids)."""
@@ -1748,7 +1859,7 @@ class IndexedSlices:
     """
 
     def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None, offsets=None,
-                 fm_grad=None, fm_sum=None):
+                 fm_grad=None, fm_sum=None, weights=None):
         """bag / bag_of (optional): POOLED slices, the gradient of a sum-pooled lookup -- values is [B, width], one row per
         bag, and occurrence i of indices takes the row of its bag: i // bag (fixed bags of `bag` ids) or bag_of[i] (int32 [n],
         ragged bags).  offsets (optional, with bag_of): the int64 [B + 1] offsets bag_of was built from -- what the one-call
@@ -1756,13 +1867,18 @@ class IndexedSlices:
         fm_grad / fm_sum (optional, together, with bag / bag_of): FM-POOLED slices, the gradient of an FM-pooled lookup whose
         rows nothing consumed -- values is g_sum [B, width] or None, fm_grad [B, width] the gradient of the FM output and
         fm_sum [B, width] the forward's sum; the gradient of an occurrence also depends on its table row
-        (ops.sgd_apply_fm_bags), so only the SGD update takes them."""
+        (ops.sgd_apply_fm_bags), so only the SGD update takes them.
+        weights (optional, with bag / bag_of, not with fm_grad): WEIGHTED pooled slices, the gradient of a weighted sum-pooled
+        lookup (ops.embedding_lookup_wsum) -- float32, one weight per occurrence of indices; the gradient of occurrence i is
+        weights[i] * values[its bag], and a zero weight means the occurrence is not applied at all."""
         if bag is not None and bag_of is not None:
             raise ValueError("give at most one of bag and bag_of")
         if offsets is not None and bag_of is None:
             raise ValueError("offsets come with bag_of (ragged bags)")
         self._check_fm(fm_grad, fm_sum, bag, bag_of)
+        self._check_weights(weights, fm_grad, bag, bag_of, indices)
         self.fm_grad, self.fm_sum = fm_grad, fm_sum
+        self.weights = weights
         self.offsets = offsets
         self.indices = indices
         self.values = values
@@ -1778,9 +1894,27 @@ class IndexedSlices:
         if fm_grad is not None and bag is None and bag_of is None:
             raise ValueError("fm_grad / fm_sum come with bag or bag_of (FM-pooled slices)")
 
+    @staticmethod
+    def _check_weights(weights, fm_grad, bag, bag_of, indices):
+        if weights is None:
+            return
+        if bag is None and bag_of is None:
+            raise ValueError("weights come with bag or bag_of (weighted pooled slices)")
+        if fm_grad is not None:
+            raise ValueError("weights do not come with fm_grad / fm_sum: there is no weighted FM-pooled gradient")
+        if weights.dtype != torch.float32:
+            raise TypeError("weights must be float32")
+        if indices is not None and weights.numel() != indices.numel():
+            raise ValueError("weights must have one entry per index (%d), got %d" % (indices.numel(), weights.numel()))
+
     @property
     def pooled(self):
         return self.bag is not None or self.bag_of is not None
+
+    @property
+    def weighted(self):
+        """Weighted pooled slices: the gradient of occurrence i is weights[i] * values[its bag]."""
+        return self.weights is not None
 
     @property
     def fm_pooled(self):
@@ -1793,13 +1927,19 @@ class IndexedSlices:
                              "table row" % what)
 
     def expanded_values(self, stream=None):
-        """Per-occurrence values [n, width] of pooled slices (every occurrence a copy of its bag's row)."""
+        """Per-occurrence values [n, width] of pooled slices (every occurrence a copy of its bag's row; of weighted slices
+        its weight times that row, ops.wbag_grad_rows)."""
         self._no_fm_pooled("have no expanded values")
         width = self.values.shape[-1]
         vals = self.values.reshape(-1, width).contiguous()
         if not self.pooled:
             return vals
         n = self.indices.numel()
+        if self.weighted:
+            w = self.weights.reshape(-1).contiguous()
+            if self.bag is not None:
+                return wbag_grad_rows(vals, w, bag=int(self.bag), stream=stream)
+            return wbag_grad_rows(vals, w, bag_of=self.bag_of.reshape(-1).contiguous(), stream=stream)
         if self.bag is not None:
             rows = torch.arange(n, dtype=torch.int64, device=vals.device) // int(self.bag)
         else:
@@ -1814,8 +1954,10 @@ class IndexedSlices:
         return tuple(self.values.shape)
 
     def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None, offsets=None, fm_grad=None,
-               fm_sum=None):
+               fm_sum=None, weights=None):
         self._check_fm(fm_grad, fm_sum, bag, bag_of)
+        self._check_weights(weights, fm_grad, bag, bag_of, indices)
+        self.weights = weights
         self.indices = indices
         self.push_indices = push_indices
         self.bag, self.bag_of, self.offsets = bag, bag_of, offsets
@@ -1829,6 +1971,9 @@ class IndexedSlices:
 
     def deduplicate(self, stream=None):
         self._no_fm_pooled("cannot be deduplicated")
+        if self.weighted:      # expanded first: ordinary unpooled slices from here on
+            self.values = self.expanded_values(stream)
+            self.bag = self.bag_of = self.offsets = self.weights = None
         if self.pooled:
             raise ValueError("pooled IndexedSlices (bag / bag_of) cannot be deduplicated: values holds one row per bag")
         ids = self.indices.reshape(-1)

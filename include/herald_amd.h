@@ -1494,6 +1494,53 @@ int ha_sgd_sparse_update_fm_bags_f32ids(float *table, int64_t rows, int64_t widt
 int ha_sgd_sparse_update_fm_bags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, int64_t n, int64_t bag,
                                         const int64_t *offsets, int64_t nbags, const float *g_sum, const float *g_fm,
                                         const float *sum, float lr, ha_stream_t stream);
+/* ---- weighted bags: the masked sum-pooled lookup of the FAE models (csrc/wbag.hip) ------------------------------------
+ * examples/ctr/models/fae_wdl_criteo.py:19-31: embedding_lookup_op, mul_op by a per-occurrence 0/1 mask, reduce_sum_op(axes=1).
+ * Bags -- fixed or ragged, exactly one of bag >= 1 and offsets / bag_of, offsets clamped -- are those of ha_gather_sum_* and
+ * ha_sgd_apply_bags; weights is float32[n], one per occurrence, in the ids' order.
+ * An occurrence is LIVE when its weight is not zero (+0.0f and -0.0f are zero, a NaN weight is not) and its id is below rows.
+ * A dead occurrence takes no part in anything: its row is not added, its gradient is not applied, and whatever its row or its
+ * bag's gradient holds (inf, NaN) does not reach a result.  This is the project's choice; the reference computes 0 * x, which
+ * agrees for finite data except for the sign of a zero in one corner (see ha_sgd_apply_wbags).
+ * Forward, per bag and column, in position order over the live occurrences:
+ *   acc = +0;  acc = fl(acc + fl(w_j * r_j))      one multiply and one add per term, each rounded, nothing contracted
+ * An empty bag or a bag with no live occurrence gives +0.  All weights 1.0f: ha_gather_sum_* bit for bit.  0/1 weights:
+ * ha_gather_sum_* on the ragged bags left when the dead occurrences are deleted.  Any width >= 1; width % 4 == 0 with 16-byte
+ * aligned table / out takes the 16-byte path.  Rules for every entry point of this section: exactly one of bag >= 1 and
+ * offsets / bag_of, n % bag == 0 and n / bag == nbags, n < 2^31, 1 <= width < 2^30, nbags >= 1 when n > 0, null pointers refused
+ * -- all checked before any device access; n == 0 returns 0 with null pointers allowed. */
+int ha_gather_wsum_f32ids(const float *table, int64_t rows, int64_t width, const float *ids, const float *weights, int64_t n,
+                          int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
+int ha_gather_wsum_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, const float *weights, int64_t n,
+                          int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
+/* The per-occurrence gradient, one elementwise launch: out[i,c] = fl(w_i * bag_grads[bag(i),c]), exactly +0.0f where w_i is
+ * zero.  bag_grads [nbags, width], out [n, width]: an ordinary unpooled gradient, what every optimizer, push path and cache path
+ * takes for weighted slices.  Fixed bags: bag >= 1, bag_of NULL; ragged: bag == 0 and bag_of = int32[n] from ha_bag_of. */
+int ha_wbag_grad_rows(const float *bag_grads, const float *weights, int64_t n, int64_t width, int64_t bag,
+                      const int32_t *bag_of, int64_t nbags, float *out, ha_stream_t stream);
+/* The fused apply: for every key k < rows, over its LIVE occurrences i in ascending order,
+ *   row = fl(row - fl(lr * fl(w_i * bag_grads[bag(i),:])))      three roundings per element
+ * and the row of a key with no live occurrence keeps its bits; no [n, width] tensor exists.  plan_ws: a FINISHED plan
+ * (ha_plan_build_*, or ha_plan_sort_* + ha_plan_finish) of the n ids, or of masked keys -- the row number of a live occurrence,
+ * any key >= rows for a dead one; dead occurrences found inside a run are skipped, so every such plan gives the same table.
+ * Bit for bit ha_wbag_grad_rows followed by ha_sgd_apply_finished whenever no table element is -0.0f: with lr < 0 that composed
+ * sequence turns a -0.0f under a dead occurrence into +0.0f, this call keeps it.  Tolerance mode 1 or 2: the entry points run
+ * exactly that composed sequence through the library's per-stream scratch (n * width floats), so long runs take the same tree
+ * as everywhere else (plan_ws, bag_of, bag_grads and weights must then be the caller's own allocations, see
+ * ha_dedup_reduce_bags).  bag_grads and weights must not alias the table. */
+int ha_sgd_apply_wbags(float *table, int64_t rows, int64_t width, void *plan_ws, int64_t n, const float *bag_grads,
+                       const float *weights, int64_t bag, const int32_t *bag_of, int64_t nbags, float lr, ha_stream_t stream);
+/* One call on the internal per-stream workspace: one small launch writes masked uint64 keys (the row number of a live
+ * occurrence, the key `rows` for a dead one), then ha_plan_sort_u64ids_lim + ha_plan_finish (+ ha_bag_of), then the apply.
+ * The dead occurrences of FAE data -- thousands of padding ids per batch -- leave the plan as one out-of-range key that the
+ * apply drops with one test instead of walking them as the batch's longest run.  Nothing is read back to the host.
+ * rows <= 2^32 - 2.  Tolerance mode: the ids are planned as they are and the composed sequence runs (see above). */
+int ha_sgd_sparse_update_wbags_f32ids(float *table, int64_t rows, int64_t width, const float *ids, const float *weights,
+                                      int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                      float lr, ha_stream_t stream);
+int ha_sgd_sparse_update_wbags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, const float *weights,
+                                      int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
+                                      float lr, ha_stream_t stream);
 /* Measurement aid (tools/bag_bench.py): column-slice width of ha_gather_sum_*'s 16-byte path, 64 / 128 / 256 floats per
  * wave; 0 = chosen from the batch (the default).  Process-wide; results do not depend on it. */
 int ha_debug_bag_slice(int floats);
