@@ -15,6 +15,12 @@ Differences that the boundary makes explicit:
   * keys / dest / grads may be device tensors (no copy) or host numpy arrays (staged over PCIe);
   * calls are asynchronous on a HIP stream; the returned handle's wait() synchronises it.
 All computation is in libherald_amd.so (csrc/cache.hip); this file only marshals arguments.
+
+Keys must name rows: every key handed to a cache (lookup, update, push keys; call by call or planned) has to be below `length`.
+The cache indexes per-row arrays by key (slot_of[length]) and nothing here or on the device checks it.  Ids that name no row by
+the id rule of include/herald_amd.h ("Which ids name a row": negative, NaN, infinite, at or beyond 2^32 -- all key 0xFFFFFFFE --
+and ids >= length) are undefined behaviour in this tier; replace padding ids before a batch reaches it.  The float32 -> key
+conversion is the library's one rule (f32_to_key), so -0.0 and -0.99 are key 0 here as everywhere.
 """
 import ctypes
 

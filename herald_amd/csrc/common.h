@@ -95,10 +95,15 @@ static inline size_t align_up(size_t x, size_t a) {
 }
 
 // ---- device helpers -------------------------------------------------------
-// (size_t)f of the reference (src/dnnl_ops/EmbeddingLookup.cpp:31) for the ids a
-// table can hold: truncation toward zero, ids < 2^32.
+// The key of a float32 id (include/herald_amd.h, "Which ids name a row"): (size_t)f of the reference
+// (src/dnnl_ops/EmbeddingLookup.cpp:31) -- truncation toward zero -- for -1 < f < 4294967295, and kDeadKey, the key
+// 64-bit ids beyond 32 bits clamp to, for every other f: NaN (both compares are false), f <= -1, f >= 4294967295
+// (no float lies between 4294967040 and 2^32) and both infinities.  The cast is evaluated for in-range values
+// only: for the rest it is undefined in C++, whatever the conversion instruction happens to return.
+constexpr uint32_t kDeadKey = 0xFFFFFFFEu;
 __device__ __forceinline__ uint32_t f32_to_key(float f) {
-    return static_cast<uint32_t>(f);
+    const bool in_range = f > -1.0f && f < 4294967296.0f;
+    return in_range ? static_cast<uint32_t>(f) : kDeadKey;
 }
 
 __device__ __forceinline__ int lane_id() {

@@ -75,8 +75,7 @@ template <typename IdT>
 __device__ __forceinline__ uint32_t to_key(IdT v);
 template <>
 __device__ __forceinline__ uint32_t to_key<float>(float v) {
-    const uint32_t k = f32_to_key(v);
-    return k == kPadKey ? 0xFFFFFFFEu : k;  // keep the pad value out of the key space
+    return f32_to_key(v);   // at most kDeadKey: the pad value is never a key
 }
 template <>
 __device__ __forceinline__ uint32_t to_key<uint64_t>(uint64_t v) {
@@ -269,7 +268,9 @@ __device__ __forceinline__ void rank_tile_body_f32(
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int j = base + threadIdx.x + k * 1024;
-            const float kv = static_cast<float>(to_key<float>(ids[min(j, n - 1)]));  // exact: a truncated float
+            // exact: a truncated float -- but for the dead key 0xFFFFFFFE, which rounds to 2^32: above every other
+            // key a float id gives (at most 4294967040), equal to nothing else, and below the pads
+            const float kv = static_cast<float>(to_key<float>(ids[min(j, n - 1)]));
             v[k] = j < n ? kv : __builtin_inff();
         }
 #pragma unroll
@@ -353,7 +354,7 @@ __device__ __forceinline__ void rank_tile_body_f32(
 #pragma unroll
         for (int k = 0; k < 32; ++k)
             r += s_part[k * 32 + il];
-        const uint32_t key = static_cast<uint32_t>(ki);
+        const uint32_t key = f32_to_key(ki);   // 2^32 (the dead key as a float) -> the dead key again
         sorted[r] = key;
         perm[r] = i;
         keys[i] = key;

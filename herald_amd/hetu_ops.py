@@ -425,10 +425,15 @@ def sgd_update_sparse(param, grad, lr, stream=None):
                                         stream=stream)
         else:
             ids = grad.indices.reshape(-1).contiguous()
-            keys = ids.to(torch.int64)
-            if ids.dtype == torch.float32:      # (as the kernels read float32 ids: toward zero, a negative one is row 0)
-                keys = keys.clamp_(min=0)
-            keys = torch.where((weights != 0) & (keys >= 0) & (keys < table.shape[0]), keys,
+            # masked keys by the id rule of include/herald_amd.h ("Which ids name a row"), as wbag.hip builds them for fixed bags:
+            # the row of a live occurrence, `rows` for a dead one (zero weight, or an id that names no row)
+            if ids.dtype == torch.float32:
+                named = (ids > -1.0) & (ids < 4294967296.0)                  # NaN: False
+                keys = torch.where(named, ids, torch.zeros_like(ids)).to(torch.int64)     # in-range values only; toward zero
+            else:
+                keys = ids.to(torch.int64)
+                named = keys >= 0                                            # (a 64-bit id beyond 2^63 - 1 reads negative)
+            keys = torch.where(named & (weights != 0) & (keys < table.shape[0]), keys,
                                torch.full_like(keys, table.shape[0]))
             plan = ops.IndexPlan(max(keys.numel(), 1), device=keys.device).sort(keys, stream, key_limit=table.shape[0])
             ops.sgd_apply_wbags(table, plan.finish(stream), values, weights, lr, bag_of=grad.bag_of, stream=stream)

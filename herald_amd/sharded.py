@@ -33,6 +33,12 @@ orders the reference can produce and makes the result reproducible.
 All arithmetic goes through an *engine*: `HipEngine` (libherald_amd kernels; the product path) or a
 test double injected by the CPU/gloo tests.  There is no CPU fallback in this module: without an
 engine argument the HIP engine is used and fails loudly when the library or a GPU is missing.
+
+Ids must name rows: the store, `FramedStep` and the pooled steps find a key's owner by its range and index per-row frames by
+key, so every id of a batch has to be below `rows`; nothing here or on the device checks it.  Ids that name no row by the id
+rule of include/herald_amd.h ("Which ids name a row": negative, NaN, infinite, at or beyond 2^32 -- all key 0xFFFFFFFE -- and
+ids >= rows) are outside this module's contract; replace padding ids before a batch reaches it (tests/test_gpu_bags.py does).
+The float32 -> key conversion is the library's one rule (f32_to_key).
 """
 import ctypes
 import os

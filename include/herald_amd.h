@@ -108,8 +108,8 @@ int SGDOptimizerSparseUpdate(DLArrayHandle param,
 
 /* Sparse optimizers on DEDUPLICATED indices (callers run IndexedSlices.deduplicate first,
  * python/hetu/gpu_links/OptimizerLink.py:60,78,95).  For all of the optimizer symbols below: an index at or
- * beyond the number of rows is skipped; negative and NaN indices are outside the contract (the conversion is
- * static_cast<uint32_t>(float), undefined for them).  Arrays need not be 16-byte aligned.  A call whose arguments are
+ * beyond the number of rows is skipped, and so is every index that names no row -- negative, NaN, infinite, at or beyond
+ * 2^32 -- by the one id rule ("Which ids name a row", below).  Arrays need not be 16-byte aligned.  A call whose arguments are
  * refused (-1) has enqueued nothing and changes nothing.
  * src/common/c_runtime_api.h:661-664 / src/ops/OptimizersSparse.cu:331-389 */
 int AdaGradOptimizerSparseUpdate(DLArrayHandle param,
@@ -194,6 +194,23 @@ int cpu_SGDOptimizerSparseUpdate(DLArrayHandle param,
  * ha_qstep_* / ha_qapply, which have their own documented tolerance classes). */
 int ha_set_tolerance_mode(int on);
 int ha_get_tolerance_mode(void);
+
+/* Which ids name a row.  Every entry point turns an id into a 32-bit KEY by one rule, and "an id >= rows" below (a zero row
+ * on lookup, skipped by every update) means "an id whose key is >= rows":
+ *   float32 id f     key = trunc(f) for -1 < f < 4294967295 -- so -0.0 and -0.99 are key 0, as the reference's (size_t)f --, and
+ *                    0xFFFFFFFE for every other f: NaN of either sign and any payload, f <= -1, f >= 4294967295, both
+ *                    infinities.  (The largest float32 below 2^32 is 4294967040 = key 0xFFFFFF00: dead by size, like rows.)
+ *   int64 / uint64   the value read as uint64; anything above 0xFFFFFFFE becomes 0xFFFFFFFE.  So -1, INT64_MIN and 2^32 + 5
+ *                    name no row, and 2^32 + 5 never aliases row 5.
+ * Key 0xFFFFFFFE is >= rows for every table the library accepts, and nothing else about it is special: -1.0 and -1 are the
+ * same id, all such occurrences of a batch are ONE run of one key in its plan (counted in n_unique, reduced by
+ * ha_dedup_reduce like any key), and ha_plan_export_f32 exports it as 4294967296.0.  The conversion never evaluates a
+ * float -> integer cast outside the cast's range (csrc/common.h f32_to_key; oracle/oracle.c and tests/special_ids.py
+ * state the same rule for the checkers).
+ * The tiers that index per-row arrays by key REQUIRE ids below rows (`length`) and do not check it on the device: the HET
+ * cache, call by call and planned (ha_cache_*: slot_of[length]), the sharded store and its framed steps (ha_shard_*:
+ * owners are found by key range) and laia (ha_laia_*).  An id that names no row is undefined behaviour there; callers
+ * replace padding ids before they hand a batch to such a tier. */
 
 /* ---- forward gather (replaces cpu_EmbeddingLookup / embedding_lookup_kernel) */
 /* out[i,:] = table[(size_t)ids[i],:], ids float32.  width % 4 == 0 takes the

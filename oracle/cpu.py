@@ -23,15 +23,16 @@ def lib():
             _build.build_oracle()
         L = ctypes.CDLL(path)
         c = ctypes
-        L.oracle_embedding_lookup.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
-        L.oracle_sgd_sparse_update.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t,
-                                               c.c_void_p, c.c_float]
+        L.oracle_embedding_lookup_rows.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
+        L.oracle_sgd_sparse_update_rows.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_size_t,
+                                                    c.c_void_p, c.c_float]
         L.oracle_unique_u64.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_void_p]
         L.oracle_unique_u64.restype = c.c_size_t
         L.oracle_ids_to_keys.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]
+        L.oracle_u64ids_to_keys.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p]
         L.oracle_dedup_reduce.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_size_t,
                                           c.c_void_p]
-        L.oracle_push_apply.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
+        L.oracle_push_apply_rows.argtypes = [c.c_void_p, c.c_size_t, c.c_size_t, c.c_void_p, c.c_size_t, c.c_void_p]
         L.oracle_partition.argtypes = [c.c_size_t, c.c_size_t, c.c_void_p]
         L.oracle_num_threads.restype = c.c_int
         _LIB = L
@@ -48,25 +49,35 @@ def _f32(a):
 
 
 def embedding_lookup(table, ids):
-    """cpu_EmbeddingLookup (src/dnnl_ops/EmbeddingLookup.cpp:16-35)."""
+    """cpu_EmbeddingLookup (src/dnnl_ops/EmbeddingLookup.cpp:16-35); an id that names no row (include/herald_amd.h,
+    "Which ids name a row") gives a zero row."""
     table = _f32(table)
     ids = _f32(ids)
     out = np.empty(ids.shape + (table.shape[1],), dtype=np.float32)
-    lib().oracle_embedding_lookup(_p(table), table.shape[1], _p(ids), ids.size, _p(out))
+    lib().oracle_embedding_lookup_rows(_p(table), table.shape[0], table.shape[1], _p(ids), ids.size, _p(out))
     return out
 
 
 def sgd_sparse_update(table, ids, grads, lr):
-    """cpu_SGDOptimizerSparseUpdate (src/dnnl_ops/Optimizers.cpp:51-74); updates `table` in place."""
+    """cpu_SGDOptimizerSparseUpdate (src/dnnl_ops/Optimizers.cpp:51-74); updates `table` in place.  An id that names
+    no row is skipped."""
     assert table.dtype == np.float32 and table.flags.c_contiguous
     ids = _f32(ids)
     grads = _f32(grads)
-    lib().oracle_sgd_sparse_update(_p(table), table.shape[1], _p(ids), ids.size, _p(grads),
-                                   ctypes.c_float(lr))
+    lib().oracle_sgd_sparse_update_rows(_p(table), table.shape[0], table.shape[1], _p(ids), ids.size, _p(grads),
+                                        ctypes.c_float(lr))
     return table
 
 
 def ids_to_keys(ids):
+    """The keys of a batch of ids by the one id rule (include/herald_amd.h, "Which ids name a row"): float32 ids (anything
+    that is not a 64-bit integer array is taken as float32, as before), or int64 / uint64 ids read as uint64."""
+    ids = np.asarray(ids)
+    if ids.dtype in (np.int64, np.uint64):
+        ids = np.ascontiguousarray(ids).reshape(-1).view(np.uint64)
+        keys = np.empty(ids.size, dtype=np.uint64)
+        lib().oracle_u64ids_to_keys(_p(ids), ids.size, _p(keys))
+        return keys
     ids = _f32(ids).reshape(-1)
     keys = np.empty(ids.size, dtype=np.uint64)
     lib().oracle_ids_to_keys(_p(ids), ids.size, _p(keys))
@@ -99,7 +110,7 @@ def push_apply(table, uniq, reduced):
     """Server `+=` of SparsePush (ps-lite/include/ps/server/PSFHandle.h:130-164)."""
     uniq = np.ascontiguousarray(uniq, dtype=np.uint64)
     reduced = _f32(reduced)
-    lib().oracle_push_apply(_p(table), table.shape[1], _p(uniq), uniq.size, _p(reduced))
+    lib().oracle_push_apply_rows(_p(table), table.shape[0], table.shape[1], _p(uniq), uniq.size, _p(reduced))
     return table
 
 

@@ -35,9 +35,14 @@ def scalar(x):
 
 
 def named_rows(ids, rows):
-    """(sel, idx) of the ids that name a row: the library converts with static_cast<uint32_t>(float), defined
-    for ids in [0, 2^32); a key >= rows is skipped."""
-    key = np.asarray(ids, dtype=np.float32).reshape(-1).astype(np.float64).astype(np.int64)
+    """(sel, idx) of the ids that name a row, by the id rule of include/herald_amd.h ("Which ids name a row"): the key
+    of a float32 id f is trunc(f) for -1 < f < 4294967295 and 0xFFFFFFFE for every other f (NaN, f <= -1, beyond 32
+    bits, the infinities); a key >= rows is skipped.  The integer cast runs on in-range values only."""
+    f = np.asarray(ids, dtype=np.float32).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        live = (f > np.float32(-1.0)) & (f < np.float32(4294967296.0))
+    key = np.full(f.size, 0xFFFFFFFE, dtype=np.int64)
+    key[live] = np.trunc(f[live]).astype(np.int64)
     sel = np.flatnonzero(key < rows)
     return sel, key[sel]
 

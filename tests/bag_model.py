@@ -5,6 +5,8 @@ Every sum is a sequential chain of float32 additions in position order, every up
 float32 subtract -- the order and the roundings the kernels are held to bit for bit."""
 import numpy as np
 
+import special_ids
+
 
 def clamp_offsets(offsets, n):
     """The bag bounds the kernels use: every offset clamped to [0, n], a bag's end to its start."""
@@ -24,11 +26,9 @@ def bag_bounds(n_or_ids_shape, offsets=None):
 
 
 def ids_to_rows(ids):
-    """(size_t)ids[i] of the reference: float32 ids truncate toward zero, integer ids are keys as they are."""
-    ids = np.asarray(ids)
-    if ids.dtype.kind == "f":
-        return ids.reshape(-1).astype(np.int64)
-    return ids.reshape(-1).astype(np.uint64).astype(np.int64)
+    """(size_t)ids[i] of the reference: float32 ids truncate toward zero, integer ids are keys as they are; an id that
+    names no row of any table (negative, NaN, infinite, beyond 32 bits) is special_ids.DEAD_KEY, never a negative index."""
+    return special_ids.rows_of(ids)
 
 
 def bag_sum(table, ids, offsets=None):

@@ -16,6 +16,7 @@ import functools
 import numpy as np
 import pytest
 
+import special_ids
 from oracle import cpu
 from oracle import optim_ref64 as ref64
 
@@ -107,7 +108,9 @@ def step32(op, a, ids, grads, t, hyper=None):
     f = np.float32
     ids = np.asarray(ids, dtype=f).reshape(-1)
     grads = np.asarray(grads, dtype=f).reshape(ids.size, a["param"].shape[1])
-    sel, idx = ref64.named_rows(ids, a["param"].shape[0])
+    key = special_ids.rows_of(ids)
+    sel = np.flatnonzero(key < a["param"].shape[0])
+    idx = key[sel]
     new = {k: a[k].copy() for k in ("param",) + STATES.get(op, ("velocity",))}
     with np.errstate(divide="ignore", invalid="ignore"):       # Lamb divides by norm(update), which may be 0
         if op == "l2":
