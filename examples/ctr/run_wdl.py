@@ -62,6 +62,12 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      sum-pooled lookup (ha_gather_wsum_*: the slot of a hot id is the padding id 0 with weight 0) and, with
                      --optimizer sgd, the fused weighted apply (ha_sgd_sparse_update_wbags_*: the dead slots leave the plan as
                      one out-of-range key); the other optimizers take the weighted gradient expanded.  --embedding hbm only.
+  --model fae_deepfm the FAE DeepFM (examples/ctr/models/fae_deepfm_avazu.py; also fae_deepfm_avazu, fae_dfm_avazu): fae_wdl's hot
+                     list and split over the DeepFM's two tables.  The first-order table is the weighted bag at width 1; the
+                     second-order table goes through the WEIGHTED FM-pooled lookup (ha_gather_wfm_*: S and Q of the cold rows,
+                     separately, because the square of the sum is taken after the hot table's half has been added) and ONE fused
+                     apply (ha_sgd_sparse_update_wfm_bags_*): no [batch * 26, d] tensor in the step.  Both tables have a hot
+                     table that trains with the tower.  --embedding hbm, --optimizer sgd.
   --model dcn        Deep & Cross (examples/ctr/models/dcn_criteo.py:8-74; the reference hard-codes d = 128 there, the
                      embedding width is a parameter here) instead of Wide & Deep.
 
@@ -232,16 +238,40 @@ class FMSumLookup(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class WeightedFMSumLookup(torch.autograd.Function):
+    """EmbeddingLookUpWeightedFMSum and EmbeddingLookUpWeightedFMSum_Gradient as one autograd node: forward returns S [B, d] and
+    Q [B, d] of one fused lookup over (ids, weights) that writes no rows; backward wraps the gradients of both as weighted
+    FM-pooled IndexedSlices in `sink` -- nothing [B * 26, d] is saved or built.  `anchor` as in FMLookup."""
+
+    @staticmethod
+    def forward(ctx, anchor, ids, weights, lookup, lookup_grad, sink):
+        batch, width = ids.shape[0], lookup.embedding.shape[1]
+        total = torch.empty((batch, width), dtype=torch.float32, device=ids.device)
+        sq = torch.empty((batch, width), dtype=torch.float32, device=ids.device)
+        lookup.compute(ids, weights, total, sq)
+        ctx.save_for_backward(ids, weights)
+        ctx.lookup_grad, ctx.sink = lookup_grad, sink
+        return total, sq
+
+    @staticmethod
+    def backward(ctx, g_total, g_sq):
+        ids, weights = ctx.saved_tensors
+        ctx.sink["grad"] = ctx.lookup_grad.compute(g_total.contiguous(), g_sq.contiguous(), ids, weights)
+        return None, None, None, None, None, None
+
+
 POOLED_MODELS = ("emb_sum_wdl",)
 FM_MODELS = ("deepfm", "emb_sum_deepfm")
 FAE_MODELS = ("fae_wdl",)
-MODEL_ALIASES = {"emb_sum_deepfm_avazu": "emb_sum_deepfm", "emb_sum_dfm_avazu": "emb_sum_deepfm", "fae_wdl_criteo": "fae_wdl"}
+FAE_FM_MODELS = ("fae_deepfm",)
+MODEL_ALIASES = {"emb_sum_deepfm_avazu": "emb_sum_deepfm", "emb_sum_dfm_avazu": "emb_sum_deepfm", "fae_wdl_criteo": "fae_wdl",
+                 "fae_deepfm_avazu": "fae_deepfm", "fae_dfm_avazu": "fae_deepfm"}
 OPTIMIZERS = ("sgd", "momentum", "nesterov", "adagrad", "adam", "adamw")
 
 
 def make_tower(model, width, seed=0):
     return {"wdl": Tower, "dcn": CrossTower, "emb_sum_wdl": SumTower, "deepfm": FMTower,
-            "emb_sum_deepfm": SumFMTower, "fae_wdl": SumTower}[model](width, seed)
+            "emb_sum_deepfm": SumFMTower, "fae_wdl": SumTower, "fae_deepfm": SumFMTower}[model](width, seed)
 
 
 def fae_hot_ids(batches, rows, rate):
@@ -429,6 +459,77 @@ def train_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_
     return losses, param, tower
 
 
+def train_fae_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every, fae_hot_rate):
+    """--model fae_deepfm (examples/ctr/models/fae_deepfm_avazu.py) with both tables in HBM.  The hot list and the split of every
+    batch are fae_wdl's (fae_hot_ids / fae_split).  First-order table [rows, 1]: EmbeddingLookUpWeightedSum over (cold_ids,
+    cold_mask) plus a hot table [num_hot, 1].  Second-order table [rows, width]: the weighted FM operator pair (WeightedFMSumLookup:
+    S and Q of the cold rows, no [B * 26, d] tensor) plus a hot table [num_hot, width] (the reference's W5), whose halves of S and Q
+    are embedding_bag over W5 and over W5 * W5 with per-sample weights 1 - cold_mask; then S = S_cold + S_hot, Q = Q_cold + Q_hot
+    and fm = 0.5 * (S*S - Q): the square of the sum is taken after the halves are added.  Both hot tables start as copies of the
+    main tables' hot rows and are trained with the tower; the main tables take the fused weighted applies.  Returns (losses,
+    second-order parameter, tower); the parameter carries `hot_table`, `hot_ids` and `first_order`, which carries its own
+    `hot_table`."""
+    dev = torch.device(device)
+    tower = make_tower("fae_deepfm", width, seed).to(dev)
+    opt = torch.optim.SGD(tower.parameters(), lr=lr)
+    batches = make_batches(min(steps + 1, 64), batch, rows, seed)
+    dev_batches = [tuple(torch.from_numpy(a).to(dev) for a in b) for b in batches]
+    if table_init is None:
+        g = torch.Generator(device=dev).manual_seed(seed + 1)
+        table_init = torch.randn((rows, width), generator=g, device=dev) * 0.01    # init.random_normal(stddev=0.01)
+    if first_order_init is None:
+        g = torch.Generator(device=dev).manual_seed(seed + 2)
+        first_order_init = torch.randn((rows, 1), generator=g, device=dev) * 0.01
+    hot = fae_hot_ids(batches, rows, fae_hot_rate)
+    splits = [tuple(torch.from_numpy(a).to(dev) for a in fae_split(b[0], hot)) for b in batches]
+    config = hetu_ops.Config(comm_mode=None)
+    param = hetu_ops.EmbeddingParameter(table=table_init.clone())
+    param.first_order = first = hetu_ops.EmbeddingParameter(table=first_order_init.clone())
+    param.hot_ids = first.hot_ids = torch.from_numpy(hot).to(dev)
+    param.hot_table = hot_table = torch.nn.Parameter(param.table[param.hot_ids].clone())
+    first.hot_table = first_hot = torch.nn.Parameter(first.table[param.hot_ids].clone())
+    opt.add_param_group({"params": [hot_table, first_hot]})
+    first_lookup = hetu_ops.EmbeddingLookUpWeightedSum(first)
+    first_lookup.forward_hook(config)
+    first_grad = hetu_ops.EmbeddingLookUpWeightedSum_Gradient(first.shape)
+    lookup = hetu_ops.EmbeddingLookUpWeightedFMSum(param)
+    lookup.forward_hook(config)
+    lookup_grad = hetu_ops.EmbeddingLookUpWeightedFMSum_Gradient(param.shape)
+    anchor = torch.zeros((), device=dev, requires_grad=True)
+    sink = {}
+    losses = []
+    t0 = time.perf_counter()
+    for k in range(steps):
+        _, dense, label = dev_batches[k % len(dev_batches)]
+        hot_rank, cold_ids, cold_mask = splits[k % len(splits)]
+        y_cold = torch.empty((batch, 1), dtype=torch.float32, device=dev)
+        first_lookup.compute(cold_ids, cold_mask, y_cold)          # the first-order term: the weighted bag at width 1
+        y_cold.requires_grad_(True)
+        total, sq = WeightedFMSumLookup.apply(anchor, cold_ids, cold_mask, lookup, lookup_grad, sink)
+        y_first = y_cold
+        if hot.size > 0:
+            # the hot halves: a cold slot reads hot row 0 with weight 0
+            idx, hw = (hot_rank - 1).clamp_(min=0), 1 - cold_mask
+            bag = torch.nn.functional.embedding_bag
+            y_first = y_cold + bag(idx, first_hot, per_sample_weights=hw, mode="sum")
+            total = total + bag(idx, hot_table, per_sample_weights=hw, mode="sum")
+            sq = sq + bag(idx, hot_table * hot_table, per_sample_weights=hw, mode="sum")
+        fm = 0.5 * (total * total - sq)
+        pred = tower(dense, total, y_first, fm)
+        loss = torch.nn.functional.binary_cross_entropy(pred, label)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        hetu_ops.sgd_update_sparse(first, first_grad.compute(y_cold.grad, cold_ids, cold_mask), lr)    # weighted pooled slices
+        hetu_ops.sgd_update_sparse(param, sink.pop("grad"), lr)          # weighted FM-pooled slices: the fused weighted FM apply
+        losses.append(float(loss.detach()))
+        if log_every and (k + 1) % log_every == 0:
+            print("step %d loss %.5f (%.1f ms/step)" % (k + 1, np.mean(losses[-log_every:]),
+                                                        1e3 * (time.perf_counter() - t0) / (k + 1)))
+    torch.cuda.synchronize()
+    return losses, param, tower
+
+
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
@@ -458,7 +559,16 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     are hot (fae_hot_ids).  The hot table [num_hot, width] is a torch parameter, initialised from the main table's rows at the
     hot ids and trained with the tower; its half of a sample's sum is embedding_bag with per-sample weights 1 - cold_mask.  The
     cold half is EmbeddingLookUpWeightedSum on the main table over (cold_ids, cold_mask), its gradient weighted pooled slices:
-    --optimizer sgd applies them fused, the others expanded.  The returned parameter carries `hot_table` and `hot_ids`."""
+    --optimizer sgd applies them fused, the others expanded.  The returned parameter carries `hot_table` and `hot_ids`.
+    model="fae_deepfm" (--model fae_deepfm), --embedding hbm with --optimizer sgd only (train_fae_deepfm): the FAE split over the
+    DeepFM's two tables, the second-order one through the weighted FM-pooled lookup and its fused apply."""
+    if model in FAE_FM_MODELS:
+        if embedding != "hbm" or optimizer != "sgd":
+            raise ValueError("%s runs with --embedding hbm and --optimizer sgd only: its weighted FM-pooled lookup is not part of "
+                             "the step engines, the PS or the cache flows, nor of the other optimizers' pooled paths (got "
+                             "--embedding %s --optimizer %s)" % (model, embedding, optimizer))
+        return train_fae_deepfm(rows, width, batch, steps, lr, seed, device, table_init, first_order_init, log_every,
+                                fae_hot_rate)
     if model in FM_MODELS:
         if embedding != "hbm" or optimizer != "sgd":
             raise ValueError("%s runs with --embedding hbm and --optimizer sgd only: its FM-pooled lookup is not part of the "
@@ -679,10 +789,11 @@ def main():
     # table with one launch per step, "queue" = the work-queue step with lookahead, ...).
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="wdl", help="wdl_criteo | dcn_criteo | emb_sum_wdl_criteo | deepfm_criteo | "
-                                                   "emb_sum_deepfm_avazu | emb_sum_dfm_avazu | fae_wdl_criteo (the reference's "
-                                                   "names) or wdl | dcn | emb_sum_wdl | deepfm | emb_sum_deepfm | fae_wdl")
+                                                   "emb_sum_deepfm_avazu | emb_sum_dfm_avazu | fae_wdl_criteo | fae_deepfm_avazu | "
+                                                   "fae_dfm_avazu (the reference's names) or wdl | dcn | emb_sum_wdl | deepfm | "
+                                                   "emb_sum_deepfm | fae_wdl | fae_deepfm")
     ap.add_argument("--fae-hot-rate", type=float, default=0.01,
-                    help="--model fae_wdl: the share of the table's rows, most frequent ids first, served by the hot table")
+                    help="--model fae_wdl / fae_deepfm: the share of the table's rows, most frequent ids first, served by the hot table")
     ap.add_argument("-b", "--batch-size", "--batch", dest="batch", type=int, default=256)
     ap.add_argument("-e", "--embedding-size", "--width", dest="width", type=int, default=128)
     ap.add_argument("-r", "--cache-limit-ratio", type=float, default=0.1,
@@ -723,9 +834,10 @@ def main():
     ap.add_argument("--local-shared", action="store_true", help="--laia with the TopkScheduler + shared-memory rings")
     args = ap.parse_args()
     model = args.model[:-len("_criteo")] if args.model.endswith("_criteo") else MODEL_ALIASES.get(args.model, args.model)
-    if model not in ("wdl", "dcn") + POOLED_MODELS + FM_MODELS + FAE_MODELS:
+    if model not in ("wdl", "dcn") + POOLED_MODELS + FM_MODELS + FAE_MODELS + FAE_FM_MODELS:
         ap.error("--model must be wdl_criteo, dcn_criteo, emb_sum_wdl_criteo, deepfm_criteo, emb_sum_deepfm_avazu, "
-                 "emb_sum_dfm_avazu, fae_wdl_criteo, wdl, dcn, emb_sum_wdl, deepfm, emb_sum_deepfm or fae_wdl")
+                 "emb_sum_dfm_avazu, fae_wdl_criteo, fae_deepfm_avazu, fae_dfm_avazu, wdl, dcn, emb_sum_wdl, deepfm, "
+                 "emb_sum_deepfm, fae_wdl or fae_deepfm")
     args.model = model
     if model in POOLED_MODELS and (args.laia or args.embedding in ("step", "step3", "queue")):
         ap.error("--model %s pools its embeddings: use --embedding hbm (the fused kernel), ps or cache; the step engines "
@@ -741,7 +853,7 @@ def main():
     args.cache = policy
     if args.optimizer != "sgd" and (args.laia or args.embedding != "hbm"):
         ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
-    if model in FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
+    if model in FM_MODELS + FAE_FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
         ap.error("--model %s runs with --embedding hbm and --optimizer sgd only" % model)
     if model in FAE_MODELS and (args.laia or args.embedding != "hbm"):
         ap.error("--model %s runs with --embedding hbm only" % model)

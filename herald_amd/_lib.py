@@ -239,6 +239,12 @@ def _declare(L):
         "ha_sgd_apply_wbags": [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64, f32, vp],
         "ha_sgd_sparse_update_wbags_f32ids": [vp, i64, i64, vp, vp, i64, vp, i64, vp, i64, f32, vp],
         "ha_sgd_sparse_update_wbags_u64ids": [vp, i64, i64, vp, vp, i64, vp, i64, vp, i64, f32, vp],
+        "ha_gather_wfm_f32ids": [vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp],
+        "ha_gather_wfm_u64ids": [vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp],
+        "ha_wfm_grad_rows": [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp],
+        "ha_sgd_apply_wfm_bags": [vp, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, f32, vp],
+        "ha_sgd_sparse_update_wfm_bags_f32ids": [vp, i64, i64, vp, vp, i64, vp, vp, i64, vp, i64, f32, vp],
+        "ha_sgd_sparse_update_wfm_bags_u64ids": [vp, i64, i64, vp, vp, i64, vp, vp, i64, vp, i64, f32, vp],
         "ha_debug_bag_slice": [c.c_int],
         "ha_lookup_sort_f32ids": [vp, i64, i64, vp, i64, vp, vp, vp],
         "ha_lookup_sort_u64ids": [vp, i64, i64, vp, i64, vp, vp, vp],

@@ -27,40 +27,12 @@
 // skipped, so any finished plan of the ids gives the same table; the one-call form plans MASKED keys (a dead occurrence
 // becomes the key `rows`), so the padding id's thousands of dead occurrences are one out-of-range key that the apply drops
 // with one test instead of walking them as the batch's longest run.
-#include "gather_dev.h"
-#include "plan_dev.h"
+#include "wbag_dev.h"
 
 namespace ha {
 
 int scratch_get(hipStream_t stream, size_t bytes, void **out);   // capi.hip
 int tolerance_tree_from();                                       // scatter.hip
-
-template <int VEC>
-struct WVec;
-template <>
-struct WVec<1> {
-    typedef float T;
-    static __device__ __forceinline__ float get(const T &v, int) { return v; }
-    static __device__ __forceinline__ void set(T &v, int, float x) { v = x; }
-};
-template <>
-struct WVec<2> {
-    typedef float T __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
-    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
-};
-template <>
-struct WVec<4> {
-    typedef float4v T;
-    static __device__ __forceinline__ float get(const T &v, int k) { return v[k]; }
-    static __device__ __forceinline__ void set(T &v, int k, float x) { v[k] = x; }
-};
-
-constexpr int kWbagWaves = 4;         // waves per workgroup of the forward and of the short-run apply
-constexpr int kWbagLongWaves = 16;
-constexpr int kWbagCoopPerWave = 8;   // occurrences per wave and round of the cooperative path
-constexpr int kWbagCoopRound = (kWbagLongWaves - 1) * kWbagCoopPerWave;      // wave 0 runs the chain only
-constexpr int kWbagLongBlocks = 256;  // workgroups that loop over the (long key, slice) items: one per compute unit
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 // ROWS: table rows requested per round (all in flight before the first add).
@@ -165,24 +137,8 @@ __global__ __launch_bounds__(256) void wbag_grad_rows_kernel(const float *__rest
     *reinterpret_cast<V *>(out + e * VEC) = o;
 }
 
-// ---- masked keys of the one-call apply --------------------------------------------------------------------------------------
-// keys[i] = the row number of a live occurrence, `dead` (>= rows) for a dead one.
-template <typename IdT>
-__global__ __launch_bounds__(256) void wbag_mask_kernel(const IdT *__restrict__ ids, const float *__restrict__ weights, int64_t n,
-                                                        uint64_t rows, uint64_t dead, uint64_t *__restrict__ keys) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= n)
-        return;
-    const uint64_t r = id_to_row<IdT>(ids[i]);
-    keys[i] = (r < rows && weights[i] != 0.f) ? r : dead;
-}
-
 // ---- apply ---------------------------------------------------------------------------------------------------------------------
-template <bool FIXED>
-__device__ __forceinline__ int wbag_bag(int i, int bag, const int32_t *__restrict__ bag_of) {
-    return FIXED ? i / bag : bag_of[i];
-}
-
+// (the masked keys of the one-call form, wbag_mask_kernel, and wbag_bag are in wbag_dev.h: wfm.hip shares them)
 // A run shorter than kPlanLongRun, by one wave: columns col .. col + VEC - 1 of every lane.  bg / wbits: lanes 0 .. len-1 hold
 // the bags and the weights of the run's occurrences in occurrence order.
 template <int VEC, int BATCH>

@@ -16,6 +16,11 @@ Mirrors (paths relative to /root/reference):
                                                   fae_wdl_criteo.py:19-31); its gradient is weighted pooled slices, applied by
                                                   one fused launch chain (ops.sgd_sparse_update_wbags) or expanded first
                                                   (unweighted_slices) for every consumer without a weighted form
+  EmbeddingLookUpWeightedFMSum / EmbeddingLookUpWeightedFMSum_Gradient  the weighted lookup consumed as reduce_sum_op(x, axes=1)
+                                                  and reduce_sum_op(mul_op(x, x), axes=1): the second-order term of the FAE
+                                                  DeepFM (examples/ctr/models/fae_deepfm_avazu.py:43-80); its gradient is
+                                                  weighted FM-pooled slices, applied by ops.sgd_sparse_update_wfm_bags on a
+                                                  device table and refused everywhere else
   ParameterServerCommunicateOp                   python/hetu/gpu_ops/ParameterServerCommunicate.py:12-250
   ParameterServerSparsePullOp                     python/hetu/gpu_ops/ParameterServerCommunicate.py:254-306
   SGD sparse dispatch of OptimizerOp              python/hetu/gpu_links/OptimizerLink.py:23-33
@@ -375,10 +380,66 @@ class EmbeddingLookUpWeightedSum_Gradient:
                                  bag_of=ops.bag_of(offsets, index.numel()), offsets=offsets, weights=weights)
 
 
+class EmbeddingLookUpWeightedFMSum(EmbeddingLookUp):
+    """embedding_lookup_op(embedding, index), mul_op by a per-occurrence weight, then reduce_sum_op(x, axes=1) and
+    reduce_sum_op(mul_op(x, x), axes=1): the second-order term of the reference's FAE DeepFM
+    (examples/ctr/models/fae_deepfm_avazu.py:43-80), which squares the sum only after the hot table's half has been added.
+    compute(ids[B, F], weights[B, F], sum_val[B, width], sq_val[B, width]) -- or ids[n], weights[n] with offsets[B + 1] for
+    ragged bags -- is ops.embedding_lookup_wfm: no [n, width] tensor.  A device table only: on the PS and cache tiers the rows
+    an update is applied to may have changed since the lookup, and what `e` means there is not decided."""
+
+    def forward_hook(self, config):
+        super().forward_hook(config)
+        if self.compute != self._compute_gpu:
+            raise ValueError("EmbeddingLookUpWeightedFMSum needs a device table (no PS, cache or prefetch tier): the pooled FM "
+                             "gradient is a function of the table row at the time of the update")
+        self.compute = self._compute_wfm
+
+    def _compute_wfm(self, ids, weights, sum_val, sq_val, stream=None, offsets=None):
+        ops.embedding_lookup_wfm(self.embedding.table, ids, weights, offsets=offsets, sum_out=sum_val, sq_out=sq_val,
+                                 stream=stream)
+        return sum_val, sq_val
+
+
+class EmbeddingLookUpWeightedFMSum_Gradient:
+    """The gradient of EmbeddingLookUpWeightedFMSum: compute(sum_grad, sq_grad, index, weights) returns WEIGHTED FM-POOLED
+    IndexedSlices -- values is the gradient of S, sq_grad the gradient of Q, both [B, width].  Nothing is computed here: the
+    per-occurrence gradient w * (sum_grad[b] + 2 * sq_grad[b] * (w * e)) also depends on the row e, which sgd_update_sparse's
+    fused apply holds in registers (ops.sgd_apply_wfm_bags)."""
+
+    def __init__(self, embed_shape):
+        self.embed_shape = embed_shape
+
+    def compute(self, sum_grad, sq_grad, index, weights, offsets=None, stream=None):
+        if isinstance(index, tuple):
+            raise TypeError("weighted FM-pooled slices carry no push indices")
+        if offsets is None:
+            if index.dim() != 2:
+                raise ValueError("fixed bags need an index of shape [B, F]; give offsets for ragged bags")
+            return ops.IndexedSlices(indices=index, values=sum_grad, dense_shape=self.embed_shape, bag=index.shape[1],
+                                     weights=weights, sq_grad=sq_grad)
+        return ops.IndexedSlices(indices=index, values=sum_grad, dense_shape=self.embed_shape,
+                                 bag_of=ops.bag_of(offsets, index.numel(), stream=stream), offsets=offsets, weights=weights,
+                                 sq_grad=sq_grad)
+
+
+def _masked_keys(ids, weights, rows):
+    """Masked keys by the id rule of include/herald_amd.h ("Which ids name a row"), as wbag.hip builds them for fixed bags: the
+    row of a live occurrence, `rows` for a dead one (zero weight, or an id that names no row)."""
+    if ids.dtype == torch.float32:
+        named = (ids > -1.0) & (ids < 4294967296.0)                  # NaN: False
+        keys = torch.where(named, ids, torch.zeros_like(ids)).to(torch.int64)     # in-range values only; toward zero
+    else:
+        keys = ids.to(torch.int64)
+        named = keys >= 0                                            # (a 64-bit id beyond 2^63 - 1 reads negative)
+    return torch.where(named & (weights != 0) & (keys < rows), keys, torch.full_like(keys, rows))
+
+
 def unweighted_slices(grad, stream=None):
     """Weighted pooled slices as ordinary UNPOOLED ones (values [n, width] = ops.wbag_grad_rows), anything else as it is.  The
     one door every consumer without a weighted form goes through -- the other optimizers, the communicate op's pushes, the
-    fuse_bags branches -- so that a weight can never be silently dropped by a sum-pooled branch."""
+    fuse_bags branches -- so that a weight can never be silently dropped by a sum-pooled branch.  Weighted FM-pooled slices
+    (sq_grad) have no expanded values and are refused here (IndexedSlices.expanded_values): their Q term is never dropped."""
     if not getattr(grad, "weighted", False):
         return grad
     return ops.IndexedSlices(indices=grad.indices, values=grad.expanded_values(stream), dense_shape=grad.dense_shape,
@@ -390,13 +451,17 @@ def _refuse_fm_pooled(name, grad):
     if getattr(grad, "fm_pooled", False):
         raise ValueError("%s: FM-pooled slices (EmbeddingLookUpFMSum_Gradient) are taken by sgd_update_sparse on a device "
                          "table only: the gradient of an occurrence depends on its table row" % name)
+    if getattr(grad, "weighted_fm", False):
+        raise ValueError("%s: weighted FM-pooled slices (EmbeddingLookUpWeightedFMSum_Gradient) are taken by sgd_update_sparse "
+                         "on a device table only: the gradient of an occurrence depends on its table row" % name)
 
 
 def sgd_update_sparse(param, grad, lr, stream=None):
     """OptimizerOp's sparse SGD branch on a device table (OptimizerLink.py:23-33): no dedup, duplicates in
     occurrence order.  Pooled slices (EmbeddingLookUpSum_Gradient) go to the bag apply: no expanded gradient is built.
     FM-pooled slices (EmbeddingLookUpFMSum_Gradient) go to the fused FM apply: the one-call form for fixed bags, sort + finish +
-    ops.sgd_apply_fm_bags for ragged ones."""
+    ops.sgd_apply_fm_bags for ragged ones.  Weighted FM-pooled slices (EmbeddingLookUpWeightedFMSum_Gradient) go to the fused
+    weighted FM apply over masked keys, ahead of the weighted branch."""
     if getattr(grad, "fm_pooled", False):
         if param.table is None:
             raise ValueError("sgd_update_sparse: FM-pooled slices need a device table")
@@ -411,6 +476,23 @@ def sgd_update_sparse(param, grad, lr, stream=None):
             plan = ops.IndexPlan(max(ids.numel(), 1), device=ids.device).sort(ids, stream).finish(stream)
             ops.sgd_apply_fm_bags(param.table, plan, g_sum, g_fm, fm_sum, lr, bag_of=grad.bag_of, stream=stream)
         return
+    if getattr(grad, "weighted_fm", False):
+        # weighted FM-pooled slices (EmbeddingLookUpWeightedFMSum_Gradient), before the weighted branch, which would drop the Q
+        # term: the one-call form for fixed bags; masked keys + sort + finish + ops.sgd_apply_wfm_bags for ragged ones
+        if param.table is None:
+            raise ValueError("sgd_update_sparse: weighted FM-pooled slices need a device table")
+        table = param.table
+        width = table.shape[1]
+        g_sum, g_sq = grad.values.reshape(-1, width).contiguous(), grad.sq_grad.reshape(-1, width).contiguous()
+        weights = grad.weights.reshape(-1).contiguous()
+        if grad.bag is not None:
+            ops.sgd_sparse_update_wfm_bags(table, grad.indices.reshape(-1, int(grad.bag)).contiguous(), g_sum, g_sq, weights, lr,
+                                           stream=stream)
+        else:
+            keys = _masked_keys(grad.indices.reshape(-1).contiguous(), weights, table.shape[0])
+            plan = ops.IndexPlan(max(keys.numel(), 1), device=keys.device).sort(keys, stream, key_limit=table.shape[0])
+            ops.sgd_apply_wfm_bags(table, plan.finish(stream), g_sum, g_sq, weights, lr, bag_of=grad.bag_of, stream=stream)
+        return
     if getattr(grad, "weighted", False):
         # weighted pooled slices (EmbeddingLookUpWeightedSum_Gradient): the fused weighted apply over masked keys -- the one-call
         # form for fixed bags; mask + sort + finish + ops.sgd_apply_wbags for ragged ones
@@ -424,17 +506,7 @@ def sgd_update_sparse(param, grad, lr, stream=None):
             ops.sgd_sparse_update_wbags(table, grad.indices.reshape(-1, int(grad.bag)).contiguous(), values, weights, lr,
                                         stream=stream)
         else:
-            ids = grad.indices.reshape(-1).contiguous()
-            # masked keys by the id rule of include/herald_amd.h ("Which ids name a row"), as wbag.hip builds them for fixed bags:
-            # the row of a live occurrence, `rows` for a dead one (zero weight, or an id that names no row)
-            if ids.dtype == torch.float32:
-                named = (ids > -1.0) & (ids < 4294967296.0)                  # NaN: False
-                keys = torch.where(named, ids, torch.zeros_like(ids)).to(torch.int64)     # in-range values only; toward zero
-            else:
-                keys = ids.to(torch.int64)
-                named = keys >= 0                                            # (a 64-bit id beyond 2^63 - 1 reads negative)
-            keys = torch.where(named & (weights != 0) & (keys < table.shape[0]), keys,
-                               torch.full_like(keys, table.shape[0]))
+            keys = _masked_keys(grad.indices.reshape(-1).contiguous(), weights, table.shape[0])
             plan = ops.IndexPlan(max(keys.numel(), 1), device=keys.device).sort(keys, stream, key_limit=table.shape[0])
             ops.sgd_apply_wbags(table, plan.finish(stream), values, weights, lr, bag_of=grad.bag_of, stream=stream)
         return

@@ -763,6 +763,127 @@ def sgd_sparse_update_wbags(table, ids, bag_grads, weights, lr, offsets=None, st
     return table
 
 
+# ---- weighted FM-pooled lookup (the second-order term of the FAE DeepFM, csrc/wfm.hip) ------------------------------------
+def embedding_lookup_wfm(table, ids, weights, offsets=None, sum_out=None, sq_out=None, stream=None):
+    """Weighted FM-pooled lookup (ha_gather_wfm_*): per bag, over its LIVE occurrences in position order (weight not zero and id
+    < rows), x = fl(w_j * r_j), S = fl(S + x), Q = fl(Q + fl(x * x)) from +0 -- S and Q leave separately because the FAE DeepFM
+    adds the hot table's halves before it squares the sum.  S is embedding_lookup_wsum bit for bit; with all weights 1, S and
+    0.5 * (S*S - Q) are embedding_lookup_fm's sum and fm.  ids / offsets / weights as in embedding_lookup_wsum.
+    Returns (S [B, width], Q [B, width])."""
+    L = _lib.load()
+    _require(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    n, bag, nbags = _bag_shape(ids, offsets)
+    _weights_of(weights, n)
+    width = table.shape[1]
+    if sum_out is None:
+        sum_out = torch.empty((nbags, width), dtype=torch.float32, device=table.device)
+    if sq_out is None:
+        sq_out = torch.empty((nbags, width), dtype=torch.float32, device=table.device)
+    for name, t in (("sum_out", sum_out), ("sq_out", sq_out)):
+        _require(t, torch.float32, name)
+        if t.numel() != nbags * width:
+            raise ValueError("%s has the wrong size" % name)
+    fn = _ids_fn(ids, L.ha_gather_wfm_f32ids, L.ha_gather_wfm_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), _ptr(weights), n, bag,
+             _ptr(offsets) if offsets is not None else None, nbags, _ptr(sum_out), _ptr(sq_out), _stream_ptr(stream)),
+          "ha_gather_wfm")
+    return sum_out, sq_out
+
+
+def _wfm_grads(g_sum, g_sq):
+    """(nbags, width) of the two [B, width] gradients of a weighted FM-pooled lookup."""
+    _require(g_sum, torch.float32, "g_sum")
+    _require(g_sq, torch.float32, "g_sq")
+    if g_sum.dim() != 2 or tuple(g_sq.shape) != tuple(g_sum.shape):
+        raise ValueError("g_sum and g_sq must both be [B, width]")
+    return g_sum.shape
+
+
+def wfm_grad_rows(g_sum, g_sq, weights, emb_rows, bag=None, bag_of=None, out=None, stream=None):
+    """The per-occurrence gradient of embedding_lookup_wfm (ha_wfm_grad_rows): with e = emb_rows[i], b the bag of i and w its
+    weight, out[i, :] = w * (g_sum[b] + 2 * (g_sq[b] * (w * e))) -- x = fl(w * e), t = fl(g_sq * x), a = fl(g_sum + fl(t + t)),
+    fl(w * a), the project's fixed order -- and exactly +0 where w is zero.  emb_rows [..., width]: the gathered rows
+    (embedding_lookup).  Give `bag` or `bag_of` as in wbag_grad_rows.  out: default a new tensor shaped as emb_rows; it may be
+    emb_rows itself (in place).  Returns out, an ordinary unpooled gradient."""
+    nbags, width = _wfm_grads(g_sum, g_sq)
+    _require(emb_rows, torch.float32, "emb_rows")
+    if emb_rows.dim() < 1 or emb_rows.shape[-1] != width:
+        raise ValueError("emb_rows must be [..., %d]" % width)
+    n = emb_rows.numel() // width
+    _weights_of(weights, n)
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != n:
+            raise ValueError("bag_of must have one entry per occurrence")
+    elif bag < 1 or n != nbags * bag:
+        raise ValueError("emb_rows must hold B * bag rows")
+    if out is None:
+        out = torch.empty_like(emb_rows)
+    _require(out, torch.float32, "out")
+    if out.numel() != n * width:
+        raise ValueError("out has the wrong size")
+    check(_lib.load().ha_wfm_grad_rows(_ptr(g_sum), _ptr(g_sq), _ptr(weights), _ptr(emb_rows), n, width,
+                                       int(bag) if bag is not None else 0, _ptr(bag_of) if bag_of is not None else None, nbags,
+                                       _ptr(out), _stream_ptr(stream)), "ha_wfm_grad_rows")
+    return out
+
+
+def _wfm_apply_args(table, g_sum, g_sq, weights):
+    _require(table, torch.float32, "table")
+    if table.dim() != 2:
+        raise ValueError("table must be 2-D")
+    nbags, width = _wfm_grads(g_sum, g_sq)
+    if width != table.shape[1]:
+        raise ValueError("g_sum and g_sq must both be [B, %d]" % table.shape[1])
+    for name, t in (("g_sum", g_sum), ("g_sq", g_sq), ("weights", weights)):
+        if t.data_ptr() < table.data_ptr() + table.numel() * 4 and table.data_ptr() < t.data_ptr() + t.numel() * 4:
+            raise ValueError("%s must not alias the table" % name)
+    return nbags, width
+
+
+def sgd_apply_wfm_bags(table, plan, g_sum, g_sq, weights, lr, bag=None, bag_of=None, stream=None):
+    """The backward of embedding_lookup_wfm fused into the sparse SGD apply (ha_sgd_apply_wfm_bags): for every key, e = its row
+    before the call and, over its live occurrences in order, row -= lr * (w * (g_sum[b] + 2 * (g_sq[b] * (w * e)))) -- bit for
+    bit embedding_lookup + wfm_grad_rows + sgd_apply(finished=True), with no [n, width] tensor; a key without live occurrence
+    keeps its bits.  plan: FINISHED, of the ids or of masked keys (a key >= rows for a dead occurrence): the same table either
+    way.  Give `bag` or `bag_of` as in sgd_apply_bags.  The table must not have changed since the lookup."""
+    nbags, width = _wfm_apply_args(table, g_sum, g_sq, weights)
+    _weights_of(weights, plan.n)
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != plan.n:
+            raise ValueError("bag_of must have one entry per planned id")
+    elif bag < 1 or plan.n != nbags * bag:
+        raise ValueError("the plan must hold B * bag ids")
+    check(_lib.load().ha_sgd_apply_wfm_bags(_ptr(table), table.shape[0], width, _ptr(plan.ws), plan.n, _ptr(g_sum), _ptr(g_sq),
+                                            _ptr(weights), int(bag) if bag is not None else 0,
+                                            _ptr(bag_of) if bag_of is not None else None, nbags, ctypes.c_float(lr),
+                                            _stream_ptr(stream)), "ha_sgd_apply_wfm_bags")
+    return table
+
+
+def sgd_sparse_update_wfm_bags(table, ids, g_sum, g_sq, weights, lr, offsets=None, stream=None):
+    """One call: masked keys + plan + sgd_apply_wfm_bags (ha_sgd_sparse_update_wfm_bags_*).  ids / offsets as in
+    embedding_lookup_wfm, g_sum and g_sq [B, width].  The dead occurrences leave the plan as one out-of-range key."""
+    L = _lib.load()
+    nbags_t, width = _wfm_apply_args(table, g_sum, g_sq, weights)
+    n, bag, nbags = _bag_shape(ids, offsets)
+    _weights_of(weights, n)
+    if nbags_t != nbags:
+        raise ValueError("g_sum and g_sq must be [B, width]")
+    fn = _ids_fn(ids, L.ha_sgd_sparse_update_wfm_bags_f32ids, L.ha_sgd_sparse_update_wfm_bags_u64ids)
+    check(fn(_ptr(table), table.shape[0], width, _ptr(ids), _ptr(weights), n, _ptr(g_sum), _ptr(g_sq), bag,
+             _ptr(offsets) if offsets is not None else None, nbags, ctypes.c_float(lr), _stream_ptr(stream)),
+          "ha_sgd_sparse_update_wfm_bags")
+    return table
+
+
 # ---- fused launches: two per training step --------------------------------------------------------
 def lookup_sort(table, ids, plan, out=None, stream=None):
     """Forward of one batch in ONE launch: out = table[ids] and plan.sort(ids)."""
@@ -1859,7 +1980,7 @@ class IndexedSlices:
     """
 
     def __init__(self, indices=None, values=None, dense_shape=None, push_indices=None, bag=None, bag_of=None, offsets=None,
-                 fm_grad=None, fm_sum=None, weights=None):
+                 fm_grad=None, fm_sum=None, weights=None, sq_grad=None):
         """bag / bag_of (optional): POOLED slices, the gradient of a sum-pooled lookup -- values is [B, width], one row per
         bag, and occurrence i of indices takes the row of its bag: i // bag (fixed bags of `bag` ids) or bag_of[i] (int32 [n],
         ragged bags).  offsets (optional, with bag_of): the int64 [B + 1] offsets bag_of was built from -- what the one-call
@@ -1870,15 +1991,21 @@ class IndexedSlices:
         (ops.sgd_apply_fm_bags), so only the SGD update takes them.
         weights (optional, with bag / bag_of, not with fm_grad): WEIGHTED pooled slices, the gradient of a weighted sum-pooled
         lookup (ops.embedding_lookup_wsum) -- float32, one weight per occurrence of indices; the gradient of occurrence i is
-        weights[i] * values[its bag], and a zero weight means the occurrence is not applied at all."""
+        weights[i] * values[its bag], and a zero weight means the occurrence is not applied at all.
+        sq_grad (optional, with weights and bag / bag_of, not with fm_grad): WEIGHTED FM-POOLED slices, the gradient of a
+        weighted FM-pooled lookup (ops.embedding_lookup_wfm) -- values is g_S [B, width], sq_grad g_Q [B, width]; the gradient of
+        occurrence i is w * (g_S[b] + 2 * g_Q[b] * (w * its table row)), so only the SGD update on a device table takes them
+        (ops.sgd_apply_wfm_bags)."""
         if bag is not None and bag_of is not None:
             raise ValueError("give at most one of bag and bag_of")
         if offsets is not None and bag_of is None:
             raise ValueError("offsets come with bag_of (ragged bags)")
         self._check_fm(fm_grad, fm_sum, bag, bag_of)
         self._check_weights(weights, fm_grad, bag, bag_of, indices)
+        self._check_sq(sq_grad, weights, fm_grad, bag, bag_of)
         self.fm_grad, self.fm_sum = fm_grad, fm_sum
         self.weights = weights
+        self.sq_grad = sq_grad
         self.offsets = offsets
         self.indices = indices
         self.values = values
@@ -1907,6 +2034,17 @@ class IndexedSlices:
         if indices is not None and weights.numel() != indices.numel():
             raise ValueError("weights must have one entry per index (%d), got %d" % (indices.numel(), weights.numel()))
 
+    @staticmethod
+    def _check_sq(sq_grad, weights, fm_grad, bag, bag_of):
+        if sq_grad is None:
+            return
+        if fm_grad is not None:
+            raise ValueError("sq_grad does not come with fm_grad / fm_sum: FM-pooled slices carry no weights")
+        if weights is None or (bag is None and bag_of is None):
+            raise ValueError("sq_grad comes with weights and bag or bag_of (weighted FM-pooled slices)")
+        if sq_grad.dtype != torch.float32:
+            raise TypeError("sq_grad must be float32")
+
     @property
     def pooled(self):
         return self.bag is not None or self.bag_of is not None
@@ -1921,7 +2059,15 @@ class IndexedSlices:
         """FM-pooled slices: the gradient of an occurrence is (values[b] + fm_grad[b] * fm_sum[b]) - fm_grad[b] * its row."""
         return self.fm_grad is not None
 
+    @property
+    def weighted_fm(self):
+        """Weighted FM-pooled slices: the gradient of occurrence i is w_i * (values[b] + 2 * sq_grad[b] * (w_i * its row))."""
+        return self.sq_grad is not None
+
     def _no_fm_pooled(self, what):
+        if self.weighted_fm:
+            raise ValueError("weighted FM-pooled IndexedSlices (sq_grad) %s: the gradient of an occurrence depends on its "
+                             "table row" % what)
         if self.fm_pooled:
             raise ValueError("FM-pooled IndexedSlices (fm_grad / fm_sum) %s: the gradient of an occurrence depends on its "
                              "table row" % what)
@@ -1954,10 +2100,12 @@ class IndexedSlices:
         return tuple(self.values.shape)
 
     def update(self, indices, values, dense_shape, push_indices=None, bag=None, bag_of=None, offsets=None, fm_grad=None,
-               fm_sum=None, weights=None):
+               fm_sum=None, weights=None, sq_grad=None):
         self._check_fm(fm_grad, fm_sum, bag, bag_of)
         self._check_weights(weights, fm_grad, bag, bag_of, indices)
+        self._check_sq(sq_grad, weights, fm_grad, bag, bag_of)
         self.weights = weights
+        self.sq_grad = sq_grad
         self.indices = indices
         self.push_indices = push_indices
         self.bag, self.bag_of, self.offsets = bag, bag_of, offsets

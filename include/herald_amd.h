@@ -1558,6 +1558,58 @@ int ha_sgd_sparse_update_wbags_f32ids(float *table, int64_t rows, int64_t width,
 int ha_sgd_sparse_update_wbags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, const float *weights,
                                       int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
                                       float lr, ha_stream_t stream);
+/* ---- weighted FM-pooled lookup: the second-order term of the FAE DeepFM (csrc/wfm.hip) ----------------------------------
+ * examples/ctr/models/fae_deepfm_avazu.py:43-80: the cold rows are multiplied by the 0/1 mask and consumed as
+ * reduce_sum_op(x, axes=1) and as reduce_sum_op(mul_op(x, x), axes=1); the square of the sum is taken only after the hot
+ * table's half has been added, so S and Q leave as two [nbags, width] tensors.  Bags, weights, the LIVE occurrences and the
+ * argument rules are those of the weighted bags above: live = weight not zero (a NaN weight is not zero) and an id that names
+ * a row below `rows` ("Which ids name a row"); a dead occurrence takes no part in anything -- its row is not added, its
+ * gradient is not applied, and whatever its row or its bag's gradients hold (inf, NaN) reaches no result.
+ * Every fl() below is one float32 rounding (__fmul_rn, __fadd_rn, __fsub_rn); there is no FMA anywhere.
+ * Forward, per bag b and column, over the live occurrences in position order, from S = +0 and Q = +0:
+ *   x = fl(w_j * r_j);   S = fl(S + x);   Q = fl(Q + fl(x * x))
+ * A bag without a live occurrence gives S = Q = +0.  out_sum is ha_gather_wsum_*'s output bit for bit for any weights; with all
+ * weights 1.0f, out_sum and fl(0.5f * fl(fl(S*S) - Q)) are ha_gather_fm_*'s out_sum and out_fm bit for bit.  Both outputs are
+ * required and must not overlap.  Any width >= 1; width % 4 == 0 with 16-byte aligned table / outputs takes the 16-byte path.
+ * rows == 0 or n == 0: both outputs are zeroed. */
+int ha_gather_wfm_f32ids(const float *table, int64_t rows, int64_t width, const float *ids, const float *weights, int64_t n,
+                         int64_t bag, const int64_t *offsets, int64_t nbags, float *out_sum, float *out_sq, ha_stream_t stream);
+int ha_gather_wfm_u64ids(const float *table, int64_t rows, int64_t width, const uint64_t *ids, const float *weights, int64_t n,
+                         int64_t bag, const int64_t *offsets, int64_t nbags, float *out_sum, float *out_sq, ha_stream_t stream);
+/* The per-occurrence gradient, one elementwise launch: an ordinary unpooled gradient [n, width].  With e = emb_rows[i,:] (row i
+ * of a gathered row buffer), b the bag of i and w = weights[i]:
+ *   x = fl(w * e);   t = fl(g_sq[b] * x);   a = fl(g_sum[b] + fl(t + t));   out[i] = fl(w * a)
+ * and out[i] is exactly +0.0f where w is zero, whatever the operands hold.  The order is this project's fixed choice, as for
+ * ha_fm_grad_rows: the reference's executor adds the two adjoints of mul_op(x, x) and the adjoint of the sum in an unspecified
+ * topological order (fl(t) + fl(t) is fl(t + t) exactly, barring overflow).  g_sum, g_sq [nbags, width]: the gradients of
+ * out_sum and out_sq.  Fixed bags: bag >= 1, bag_of NULL; ragged: bag == 0 and bag_of = int32[n] from ha_bag_of.  out may be
+ * emb_rows itself (in place); it must not alias g_sum, g_sq or weights.  width % 4 == 0 with every pointer 16-byte aligned
+ * takes 16-byte accesses. */
+int ha_wfm_grad_rows(const float *g_sum, const float *g_sq, const float *weights, const float *emb_rows, int64_t n,
+                     int64_t width, int64_t bag, const int32_t *bag_of, int64_t nbags, float *out, ha_stream_t stream);
+/* The fused apply, two launches over a FINISHED plan (of the n ids, or of masked keys: any key >= rows for a dead occurrence).
+ * For every key k < rows: e = table[k,:] AS IT IS BEFORE THE CALL and acc = e; over the key's LIVE occurrences in ascending
+ * occurrence order g as above computed from this e, never from acc, then acc = fl(acc - fl(lr * g)); the row is written once.
+ * A key without a live occurrence keeps its bits; dead occurrences inside a run are skipped, so every finished plan of the ids
+ * gives the same table as a plan of masked keys.  No [n, width] tensor exists.  While the table has not changed since the
+ * gather this is bit for bit ha_gather_*, ha_wfm_grad_rows, ha_sgd_apply_finished -- except the corner of ha_sgd_apply_wbags:
+ * with lr < 0 a -0.0f element under a dead occurrence keeps its sign here and loses it in the composed sequence.
+ * Tolerance mode 1 or 2: the entry points run exactly that composed sequence through the library's per-stream scratch (n *
+ * width floats: the rows, then the gradient in place); plan_ws, bag_of, the gradients and weights must then be the caller's own
+ * allocations (see ha_dedup_reduce_bags).  g_sum, g_sq and weights must not alias the table. */
+int ha_sgd_apply_wfm_bags(float *table, int64_t rows, int64_t width, void *plan_ws, int64_t n, const float *g_sum,
+                          const float *g_sq, const float *weights, int64_t bag, const int32_t *bag_of, int64_t nbags, float lr,
+                          ha_stream_t stream);
+/* One call on the internal per-stream workspace: masked keys (ha_sgd_sparse_update_wbags_*'s rule: the row number of a live
+ * occurrence, the key `rows` for a dead one), ha_plan_sort_u64ids_lim with key_limit = rows, ha_plan_finish (+ ha_bag_of for
+ * ragged bags), then the apply.  Nothing is read back to the host.  rows <= 2^32 - 2.  Tolerance mode: the ids are planned as
+ * they are and the composed sequence runs (see above). */
+int ha_sgd_sparse_update_wfm_bags_f32ids(float *table, int64_t rows, int64_t width, const float *ids, const float *weights,
+                                         int64_t n, const float *g_sum, const float *g_sq, int64_t bag, const int64_t *offsets,
+                                         int64_t nbags, float lr, ha_stream_t stream);
+int ha_sgd_sparse_update_wfm_bags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, const float *weights,
+                                         int64_t n, const float *g_sum, const float *g_sq, int64_t bag, const int64_t *offsets,
+                                         int64_t nbags, float lr, ha_stream_t stream);
 /* Measurement aid (tools/bag_bench.py): column-slice width of ha_gather_sum_*'s 16-byte path, 64 / 128 / 256 floats per
  * wave; 0 = chosen from the batch (the default).  Process-wide; results do not depend on it. */
 int ha_debug_bag_slice(int floats);
