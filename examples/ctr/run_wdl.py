@@ -533,7 +533,8 @@ def train_fae_deepfm(rows, width, batch, steps, lr, seed, device, table_init, fi
 def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, cache="LRU", bound=0,
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
-          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False, first_order_init=None, fae_hot_rate=0.01):
+          opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False, first_order_init=None, fae_hot_rate=0.01,
+          ps_fuse_wbags=False):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -555,11 +556,14 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     the same bits.
     model="deepfm" (--model deepfm): DeepFM, --embedding hbm with --optimizer sgd only (train_deepfm); first_order_init: its
     first-order table [rows, 1] (default: N(0, 0.01) from seed + 2), table_init the second-order one.
-    model="fae_wdl" (--model fae_wdl), --embedding hbm only: the int(fae_hot_rate * rows) most frequent ids of the run's batches
+    model="fae_wdl" (--model fae_wdl), --embedding hbm -- or --embedding ps with ps_fuse_wbags (--ps-fuse-wbags), see below --: the int(fae_hot_rate * rows) most frequent ids of the run's batches
     are hot (fae_hot_ids).  The hot table [num_hot, width] is a torch parameter, initialised from the main table's rows at the
     hot ids and trained with the tower; its half of a sample's sum is embedding_bag with per-sample weights 1 - cold_mask.  The
     cold half is EmbeddingLookUpWeightedSum on the main table over (cold_ids, cold_mask), its gradient weighted pooled slices:
     --optimizer sgd applies them fused, the others expanded.  The returned parameter carries `hot_table` and `hot_ids`.
+    With ps_fuse_wbags on --embedding ps the cold table lives behind the sharded store, as the reference keeps it on ctx=ht.cpu(0):
+    the communicate op is given the COLD ids and the cold mask of batch k + 1 and bag=26, pulls weighted pooled rows
+    (store.pull_wsum) and pushes the weighted pooled slices as they are (push_wbags): no [batch * 26, width] tensor either way.
     model="fae_deepfm" (--model fae_deepfm), --embedding hbm with --optimizer sgd only (train_fae_deepfm): the FAE split over the
     DeepFM's two tables, the second-order one through the weighted FM-pooled lookup and its fused apply."""
     if model in FAE_FM_MODELS:
@@ -578,9 +582,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     dev = torch.device(device)
     pooled = model in POOLED_MODELS
     fae = model in FAE_MODELS
-    if fae and embedding != "hbm":
-        raise ValueError("%s runs with --embedding hbm only: the weighted sum-pooled lookup has no form on the step engines and "
-                         "no pooled form on the PS or the cache tiers (got --embedding %s)" % (model, embedding))
+    if fae and not (embedding == "hbm" or (embedding == "ps" and ps_fuse_wbags)):
+        raise ValueError("%s runs with --embedding hbm, or with --embedding ps and --ps-fuse-wbags (ps_fuse_wbags=True): the "
+                         "weighted sum-pooled lookup has no form on the step engines and no pooled form on the cache tiers (got "
+                         "--embedding %s)" % (model, embedding))
     if optimizer not in OPTIMIZERS:
         raise ValueError("optimizer must be one of %s, got %r" % (", ".join(OPTIMIZERS), optimizer))
     if optimizer != "sgd" and embedding != "hbm":
@@ -608,6 +613,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     if table_init is None:
         g = torch.Generator(device=dev).manual_seed(seed + 1)
         table_init = torch.randn((rows, width), generator=g, device=dev) * 0.01    # init.random_normal(stddev=0.01)
+    splits = None
+    if fae:      # the hot list from the run's batches, every batch split by it
+        hot = fae_hot_ids(batches, rows, fae_hot_rate)
+        splits = [tuple(torch.from_numpy(a).to(dev) for a in fae_split(b[0], hot)) for b in batches]
     if embedding in ("hbm", "step", "step3", "queue"):
         param = hetu_ops.EmbeddingParameter(table=table_init.clone())
         config = hetu_ops.Config(comm_mode=None)
@@ -621,19 +630,28 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                  cache_limit=cache_limit if cache_limit is not None else
                                  max(rows // 10, batch * NFIELD * (2 if cache_planned and bsp < 0 else 1)),
                                  cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned, cache_fuse_bags=cache_fuse_bags,
-                                 ps_fuse_bags=ps_fuse_bags, cache_fuse_bag_calls=cache_fuse_bag_calls)
-        comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: ids_of(state["k"] + 1),
-                                                     peek_ids=lambda j: ids_of(state["k"] + 1 + j),
-                                                     bag=NFIELD if pooled and embedding in ("cache", "ps") else None)
+                                 ps_fuse_bags=ps_fuse_bags, cache_fuse_bag_calls=cache_fuse_bag_calls,
+                                 ps_fuse_wbags=ps_fuse_wbags)
         barrier = dist.barrier if world > 1 else (lambda: None)
-        comm.forward_hook(config, first_ids=ids_of(0), barrier=barrier)
+        if fae:
+            # the cold table behind the store: the op pulls and pushes the COLD ids with their mask, weighted and pooled
+            def cold_of(k, what):
+                return splits[k % len(splits)][what]
+            comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: cold_of(state["k"] + 1, 1),
+                                                         peek_ids=lambda j: cold_of(state["k"] + 1 + j, 1), bag=NFIELD,
+                                                         next_weights=lambda: cold_of(state["k"] + 1, 2))
+            comm.forward_hook(config, first_ids=cold_of(0, 1), barrier=barrier, first_weights=cold_of(0, 2))
+        else:
+            comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: ids_of(state["k"] + 1),
+                                                         peek_ids=lambda j: ids_of(state["k"] + 1 + j),
+                                                         bag=NFIELD if pooled and embedding in ("cache", "ps") else None)
+            comm.forward_hook(config, first_ids=ids_of(0), barrier=barrier)
     hot_table = None
     if fae:
-        # the hot list from the run's batches, every batch split by it; the hot table starts as the main table's hot rows
-        hot = fae_hot_ids(batches, rows, fae_hot_rate)
-        splits = [tuple(torch.from_numpy(a).to(dev) for a in fae_split(b[0], hot)) for b in batches]
+        # the hot table starts as the main table's hot rows
         param.hot_ids = torch.from_numpy(hot).to(dev)
-        param.hot_table = hot_table = torch.nn.Parameter(param.table[param.hot_ids].clone())
+        param.hot_table = hot_table = torch.nn.Parameter(
+            (param.table if param.table is not None else table_init)[param.hot_ids].clone())
         opt.add_param_group({"params": [hot_table]})
         lookup = hetu_ops.EmbeddingLookUpWeightedSum(param)
         lookup_grad = hetu_ops.EmbeddingLookUpWeightedSum_Gradient(param.shape)
@@ -818,6 +836,10 @@ def main():
     ap.add_argument("--no-ps-fuse-bags", action="store_true",
                     help="--embedding ps with --model emb_sum_wdl: pull per-occurrence rows and push the expanded gradient "
                          "instead of the store's pooled pull_sum / push_bags (the same bits)")
+    ap.add_argument("--ps-fuse-wbags", action="store_true",
+                    help="--embedding ps with --model fae_wdl: the cold table behind the sharded store -- the communicate op "
+                         "pulls weighted pooled rows (pull_wsum) and pushes the weighted pooled gradient as it is (push_wbags), "
+                         "no [batch * 26, width] tensor; without it --model fae_wdl runs on --embedding hbm only")
     ap.add_argument("--cache-fuse-bag-calls", action="store_true",
                     help="--embedding cache with --model emb_sum_wdl where the cache is used call by call (no --cache-planned, "
                          "lfu / lfuopt at --bsp -1, world size > 1): pull pooled rows (embedding_lookup_sum) and push the "
@@ -855,8 +877,8 @@ def main():
         ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
     if model in FM_MODELS + FAE_FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
         ap.error("--model %s runs with --embedding hbm and --optimizer sgd only" % model)
-    if model in FAE_MODELS and (args.laia or args.embedding != "hbm"):
-        ap.error("--model %s runs with --embedding hbm only" % model)
+    if model in FAE_MODELS and (args.laia or not (args.embedding == "hbm" or (args.embedding == "ps" and args.ps_fuse_wbags))):
+        ap.error("--model %s runs with --embedding hbm, or with --embedding ps and --ps-fuse-wbags" % model)
     if args.nepoch > 0:
         args.steps *= args.nepoch
     cache_limit = max(int(args.cache_limit_ratio * args.rows), args.batch * NFIELD)
@@ -875,7 +897,7 @@ def main():
                        log_every=max(1, args.steps // 10), model=args.model, bsp=args.bsp if comm is not None else 0,
                        cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer,
                        ps_fuse_bags=not args.no_ps_fuse_bags, cache_fuse_bag_calls=args.cache_fuse_bag_calls,
-                       fae_hot_rate=args.fae_hot_rate)[0]
+                       fae_hot_rate=args.fae_hot_rate, ps_fuse_wbags=args.ps_fuse_wbags)[0]
     if local_rank == 0:
         print("first 10 steps: loss %.5f   last 10 steps: loss %.5f" % (np.mean(losses[:10]), np.mean(losses[-10:])))
 

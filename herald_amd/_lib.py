@@ -239,6 +239,8 @@ def _declare(L):
         "ha_sgd_apply_wbags": [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64, f32, vp],
         "ha_sgd_sparse_update_wbags_f32ids": [vp, i64, i64, vp, vp, i64, vp, i64, vp, i64, f32, vp],
         "ha_sgd_sparse_update_wbags_u64ids": [vp, i64, i64, vp, vp, i64, vp, i64, vp, i64, f32, vp],
+        "ha_gather_wsum_u32keys": [vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp],
+        "ha_dedup_reduce_wbags": [vp, i64, vp, vp, i64, i64, vp, i64, f32, vp, vp],
         "ha_gather_wfm_f32ids": [vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp],
         "ha_gather_wfm_u64ids": [vp, i64, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp],
         "ha_wfm_grad_rows": [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp],

@@ -28,10 +28,11 @@ Mirrors (paths relative to /root/reference):
                                                   straight from the pooled gradient of EmbeddingLookUpSum_Gradient)
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
-cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and four switches of this build: cache_plan_ahead (the cache's
+cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and five switches of this build: cache_plan_ahead (the cache's
 planned flow), cache_fuse_bags (with it, at bsp 0 and on the LRU asp chain: a sum-pooled lookup is pulled and pushed pooled, see
-Config), cache_fuse_bag_calls (the same through the cache's call-by-call interface, off by default) and
-ps_fuse_bags (the same on the plain PS flavour, every schedule).  The data loader contract is the reference's
+Config), cache_fuse_bag_calls (the same through the cache's call-by-call interface, off by default),
+ps_fuse_bags (the same on the plain PS flavour, every schedule) and ps_fuse_wbags (the WEIGHTED sum-pooled lookup of the FAE
+models pulled and pushed pooled on the plain PS flavour).  The data loader contract is the reference's
 `get_arr` / `get_next_arr` (python/hetu/dataloader.py:63-98): `next_ids()` returns the ids of the batch
 after the current one.  Everything computed goes through libherald_amd.so.
 """
@@ -47,7 +48,7 @@ from .sharded import ShardedEmbedding
 class Config:
     def __init__(self, comm_mode=None, bsp=0, prefetch=True, cstable_policy=None, cache_bound=100, cache_limit=0,
                  use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False, cache_fuse_bags=True,
-                 ps_fuse_bags=True, cache_fuse_bag_calls=False):
+                 ps_fuse_bags=True, cache_fuse_bag_calls=False, ps_fuse_wbags=True):
         self.comm_mode, self.bsp, self.prefetch = comm_mode, bsp, prefetch
         # not a HetuConfig field: the cache's PLANNED flow (csrc/cache_block.hip) for the bsp-prefetch schedule -- the bookkeeping
         # of batch k + 1 runs on a side stream beside the model's step on batch k.  Needs ids one batch further ahead than
@@ -75,11 +76,18 @@ class Config:
         # What crosses the fabric does not change -- rows per unique key --, the same bits.  False: per-occurrence rows, a
         # summing pass, the expanded gradient.
         self.ps_fuse_bags = ps_fuse_bags
+        # the weighted counterpart on the plain PS flavour (the cold table of the FAE models): a communicate op that was told its
+        # bag size AND the weights of the batches it pulls (ParameterServerCommunicateOp(..., bag=F, next_weights=...)) pulls
+        # weighted pooled rows (ShardedEmbedding.pull_wsum) and pushes weighted pooled slices as they are (push_wbags), and
+        # without prefetch EmbeddingLookUpWeightedSum pulls them itself (ragged bags too).  The same rows per unique key cross
+        # the fabric, the same bits.  False: per-occurrence rows, a weighted summing pass, the expanded gradient.
+        self.ps_fuse_wbags = ps_fuse_wbags
         self.cstable_policy, self.cache_bound, self.cache_limit = cstable_policy, cache_bound, cache_limit
         self.use_sparse_pull = use_sparse_pull
         self.cache_perf_enable = cache_perf_enable        # executor.py: cache_perf_enable (run_hetu.py:508-515 dumps the dicts)
         self.ps_map = {}
         self.ps_pooled = {}           # parameter -> bag size: its ps_map buffer holds POOLED rows [B, width]
+        self.ps_wpooled = {}          # parameter -> bag size: its ps_map buffer holds WEIGHTED pooled rows [B, width]
 
 
 class EmbeddingParameter:
@@ -330,8 +338,11 @@ class EmbeddingLookUpWeightedSum(EmbeddingLookUp):
     compute(ids[B, F], weights[B, F], output_val[B, width]) -- or ids[n], weights[n] with offsets[B + 1] for ragged bags.  With a
     device table it is the fused kernel (ops.embedding_lookup_wsum): a dead occurrence (zero weight, or id >= rows) takes no
     part.  On the PS, cache and prefetched paths the per-occurrence rows arrive as EmbeddingLookUp delivers them and the same
-    kernel sums them out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  Those tiers have no
-    pooled weighted form: a communicate op that pulls POOLED rows (bag=) cannot serve this operator and is refused."""
+    kernel sums them out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  The plain PS
+    flavour has a pooled weighted form (Config.ps_fuse_wbags): with prefetch the buffer of a communicate op that was given
+    bag= and next_weights= already holds the weighted pooled rows (store.pull_wsum) and is copied as it is; without prefetch
+    the rows come from store.pull_wsum directly, ragged bags included.  The cache tiers have none.  A communicate op that
+    pulls rows pooled WITHOUT weights (bag= alone) cannot serve this operator and is refused."""
 
     def forward_hook(self, config):
         super().forward_hook(config)
@@ -346,6 +357,14 @@ class EmbeddingLookUpWeightedSum(EmbeddingLookUp):
         if getattr(self.config, "ps_pooled", {}).get(self.embedding) is not None:
             raise ValueError("EmbeddingLookUpWeightedSum: the communicate op pulls pooled rows (bag=%d), which carry no weights; "
                              "build it without bag=" % self.config.ps_pooled[self.embedding])
+        wbag = getattr(self.config, "ps_wpooled", {}).get(self.embedding)
+        if self._rows_compute == self._compute_prefetched and wbag is not None:
+            if offsets is not None or ids.dim() != 2 or ids.shape[1] != wbag:
+                raise ValueError("EmbeddingLookUpWeightedSum: the communicate op pulls weighted pooled rows for fixed bags of "
+                                 "%d ids" % wbag)
+            return self._compute_prefetched(ids, output_val, stream)      # a weighted pooled buffer, as it is
+        if self._rows_compute == self._compute_sparsepull_from_ps and getattr(self.config, "ps_fuse_wbags", True):
+            return self.embedding.store.pull_wsum(ids, weights.reshape(ids.shape), offsets=offsets, out=output_val)
         n, width = ids.numel(), self.embedding.shape[1]
         if self._pos is None or self._pos.numel() < n or self._pos.device != output_val.device:
             self._pos = torch.arange(max(n, 1), dtype=torch.int64, device=output_val.device)
@@ -636,7 +655,7 @@ def adamw_update_sparse(param, grad, expavg, expavgsq, lr, beta1, beta2, beta1t,
 
 
 class ParameterServerCommunicateOp:
-    def __init__(self, parameter, learning_rate, next_ids, peek_ids=None, bag=None):
+    def __init__(self, parameter, learning_rate, next_ids, peek_ids=None, bag=None, next_weights=None):
         """peek_ids(j) (optional, Config.cache_plan_ahead): the ids of the batch j batches after the one next_ids() returns
         (peek_ids(0) = that batch itself), without advancing the loader; None when there is none.
         bag (optional): the embedding is read through a sum-pooled lookup (EmbeddingLookUpSum) with fixed bags of `bag` ids --
@@ -646,23 +665,36 @@ class ParameterServerCommunicateOp:
         LFU / LFUOpt at bsp < 0, the cache over a sharded store, laia push plans) with Config.cache_fuse_bag_calls; on every
         other path it changes nothing.
         Without bag= the op's pulls and pushes are per occurrence as they always were; the lookup without prefetch
-        (EmbeddingLookUpSum -> store.pull_sum) does not pass through this op and follows Config.ps_fuse_bags alone."""
+        (EmbeddingLookUpSum -> store.pull_sum) does not pass through this op and follows Config.ps_fuse_bags alone.
+        next_weights (optional, with bag=): the embedding is read through a WEIGHTED sum-pooled lookup
+        (EmbeddingLookUpWeightedSum); next_weights() returns the weights [B, bag] of the batch that the latest next_ids() call
+        returned.  On the plain PS flavour with Config.ps_fuse_wbags the op then pulls weighted pooled rows
+        (store.pull_wsum; sparse_pull_val is [B, width], recorded in config.ps_wpooled, not ps_pooled) and pushes weighted
+        pooled slices as they are, -lr included (store.push_wbags); with ps_fuse_wbags=False it moves per-occurrence rows and
+        the expanded gradient, as an op without bag= does (rows pooled without weights would be wrong for this lookup).  The
+        cache flavour has no pooled weighted form and refuses next_weights.  Without bag= it is ignored."""
         self.parameter = parameter
         self.learning_rate = -learning_rate                           # :24
         self.next_ids = next_ids
+        self.next_weights = next_weights
         self.peek_ids = peek_ids
         self._peek_offset = 1
         self.bag = int(bag) if bag is not None else None
         self._bag = None              # the bag size while pooled rows are pulled and pushed (forward_hook decides)
         self._ps_bags = False         # ... by the plain PS flavour (store.pull_sum / push_bags)
+        self._ps_wbags = False        # ... weighted, by the plain PS flavour (store.pull_wsum / push_wbags)
+        self._first_weights = None    # the weights of an explicit first batch (forward_hook(first_ids=, first_weights=))
         self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
         self._chain = False           # the planned flow of the asp schedule: _planned = ids of a push-pull chain's batches
         self._bag_calls = False       # pooled rows through the call-by-call cache (Config.cache_fuse_bag_calls)
 
-    def forward_hook(self, config, first_ids=None, barrier=lambda: None):   # :130-242
+    def forward_hook(self, config, first_ids=None, barrier=lambda: None, first_weights=None):   # :130-242
         self.config, self.barrier = config, barrier
         p = self.parameter
         self.use_cache_table = config.cstable_policy is not None and p.is_embed
+        if self.use_cache_table and self.next_weights is not None:
+            raise ValueError("ParameterServerCommunicateOp(next_weights=): the cache tiers have no pooled weighted form; build "
+                             "the op without next_weights (weighted slices are then expanded before every push)")
         if self.use_cache_table:
             width = p.shape[1]
             store = p.store
@@ -714,7 +746,14 @@ class ParameterServerCommunicateOp:
                 self._bag, self._bag_calls = self.bag, True       # the call-by-call flow, pooled
         else:
             self._push, self._pull, self._push_pull = self._push_sparse, self._pull_sparse, self._push_pull_sparse
-            if self.bag is not None and getattr(config, "ps_fuse_bags", True):
+            if self.bag is not None and self.next_weights is not None:
+                if getattr(config, "ps_fuse_wbags", True):
+                    self._bag, self._ps_wbags = self.bag, True
+                    if config.prefetch and first_ids is not None:
+                        if first_weights is None:
+                            raise ValueError("ParameterServerCommunicateOp(next_weights=): first_ids come with first_weights")
+                        self._first_weights = first_weights
+            elif self.bag is not None and getattr(config, "ps_fuse_bags", True):
                 self._bag, self._ps_bags = self.bag, True
             # :235-242: bsp >= 0 -> ssp (push, ssp_sync(version), pull), else asp (push_pull) when prefetching
             if config.prefetch and config.bsp >= 0:
@@ -733,7 +772,10 @@ class ParameterServerCommunicateOp:
                     raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
                                      % (self._bag, self._bag, tuple(first.shape)))
                 self.sparse_pull_val = torch.empty((first.shape[0], p.shape[1]), dtype=torch.float32, device=first.device)
-                config.ps_pooled[p] = self._bag
+                if self._ps_wbags:
+                    config.ps_wpooled[p] = self._bag
+                else:
+                    config.ps_pooled[p] = self._bag
             else:
                 self.sparse_pull_val = torch.empty(tuple(first.shape) + (p.shape[1],), dtype=torch.float32,
                                                    device=first.device)
@@ -755,12 +797,17 @@ class ParameterServerCommunicateOp:
         pooled by the op's own bag size stay [B, width] -- on the PS flavour ragged slices that carry their offsets too --;
         -lr is applied to those rows only, which is the same product for every occurrence of a bag.
         FM-pooled slices are refused: the rows a push is applied to may have changed since the lookup.  Weighted pooled slices
-        (EmbeddingLookUpWeightedSum_Gradient) are expanded first on every store and schedule: no tier has a pooled weighted form."""
+        (EmbeddingLookUpWeightedSum_Gradient) stay pooled on the plain PS flavour when the op pulls weighted pooled rows (bag=
+        and next_weights=, Config.ps_fuse_wbags) and their bag is the op's, or they are ragged and carry offsets; everywhere else
+        they are expanded first.  Such an op expands every OTHER pooled slice: its pushes have no unweighted pooled form."""
         _refuse_fm_pooled("ParameterServerCommunicateOp", grad)
+        if self._ps_wbags and getattr(grad, "weighted", False) and \
+                (grad.bag == self._bag if grad.bag is not None else grad.offsets is not None):
+            return grad
         grad = unweighted_slices(grad)
         if not getattr(grad, "pooled", False):
             return grad
-        if self._bag is not None and grad.bag == self._bag:
+        if self._bag is not None and grad.bag == self._bag and not self._ps_wbags:
             return grad
         if self._ps_bags and grad.bag is None and grad.offsets is not None:
             return grad
@@ -768,6 +815,10 @@ class ParameterServerCommunicateOp:
                                  push_indices=grad.push_indices)
 
     def _mult_lr(self, grad):
+        if self._ps_wbags and getattr(grad, "weighted", False):
+            # (what _per_occurrence left weighted: -lr goes to push_wbags, which rounds fl(-lr * fl(w * g)) as wbag_grad_rows,
+            # scale_ and a push with scale 1 do; the caller's values and weights are not written)
+            return
         scale_(grad.values, self.learning_rate)
 
     def _compute_asp_prefetch(self, grad):
@@ -948,6 +999,17 @@ class ParameterServerCommunicateOp:
 
     # -- plain PS flavour (SparsePush / SparsePull / SSPushPull, :74-111); values are already scaled
     def _push_sparse(self, grad):
+        if self._ps_wbags and getattr(grad, "weighted", False):      # (what _per_occurrence left weighted: values is [B, width])
+            width, store = self.parameter.shape[1], self.parameter.store
+            if grad.bag is not None:
+                ids = grad.indices.reshape(-1, int(grad.bag))
+                store.push_wbags(ids, grad.values.reshape(-1, width), grad.weights.reshape(ids.shape).contiguous(),
+                                 lr=-self.learning_rate)
+            else:
+                ids = grad.indices.reshape(-1)
+                store.push_wbags(ids, grad.values.reshape(-1, width), grad.weights.reshape(-1).contiguous(),
+                                 lr=-self.learning_rate, offsets=grad.offsets)
+            return None
         if self._ps_bags and getattr(grad, "pooled", False):      # (what _per_occurrence left pooled: values is [B, width])
             width = self.parameter.shape[1]
             if grad.bag is not None:
@@ -967,6 +1029,15 @@ class ParameterServerCommunicateOp:
                 raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
                                  % (self._bag, self._bag, tuple(ids.shape)))
             self.parameter.store.pull_sum(ids, out=self.sparse_pull_val)
+            return None
+        if self._ps_wbags:
+            if ids.dim() != 2 or ids.shape[1] != self._bag:
+                raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
+                                 % (self._bag, self._bag, tuple(ids.shape)))
+            weights, self._first_weights = self._first_weights, None
+            if weights is None:
+                weights = self.next_weights()      # of the batch the latest next_ids() call returned: these ids
+            self.parameter.store.pull_wsum(ids, weights, out=self.sparse_pull_val)
             return None
         self.sparse_pull_val.copy_(self.parameter.store.pull(ids))
         return None

@@ -763,6 +763,77 @@ def sgd_sparse_update_wbags(table, ids, bag_grads, weights, lr, offsets=None, st
     return table
 
 
+# ---- weighted bags on the row-sharded table (the end kernels of pull_wsum / push_wbags, csrc/wshard.hip) -------------------
+def gather_wsum_u32keys(rows_buf, keys_i32, weights, bag=None, offsets=None, out=None, stream=None):
+    """embedding_lookup_wsum over a buffer of rows named by uint32 keys held in an int32 tensor (a plan's inverse(): the
+    pull of the sharded store sums a batch's weighted bags straight out of the unique rows it received).  keys / bag /
+    offsets as in gather_sum_u32keys, weights float32 with one entry per key.  All weights 1: gather_sum_u32keys bit for
+    bit.  Returns out [B, width]."""
+    L = _lib.load()
+    _require(rows_buf, torch.float32, "rows_buf")
+    if rows_buf.dim() != 2:
+        raise ValueError("rows_buf must be 2-D")
+    _require(keys_i32, torch.int32, "keys")
+    n = keys_i32.numel()
+    _weights_of(weights, n)
+    if offsets is not None:
+        if bag is not None:
+            raise ValueError("give at most one of bag and offsets")
+        _require(offsets, torch.int64, "offsets")
+        if offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("ragged bags need offsets of shape [B + 1]")
+        bag, nbags = 0, offsets.numel() - 1
+    else:
+        if bag is None:
+            if keys_i32.dim() != 2:
+                raise ValueError("fixed bags need keys of shape [B, F] or bag=F; give offsets for ragged bags")
+            bag = keys_i32.shape[1]
+        bag = int(bag)
+        if bag < 1 or n % bag:
+            raise ValueError("%d keys are not bags of %d" % (n, bag))
+        nbags = n // bag
+    width = rows_buf.shape[1]
+    if out is None:
+        out = torch.empty((nbags, width), dtype=torch.float32, device=rows_buf.device)
+    _require(out, torch.float32, "out")
+    if out.numel() != nbags * width:
+        raise ValueError("out has the wrong size")
+    check(L.ha_gather_wsum_u32keys(_ptr(rows_buf), rows_buf.shape[0], width, _ptr(keys_i32), _ptr(weights), n, bag,
+                                   _ptr(offsets) if offsets is not None else None, nbags, _ptr(out), _stream_ptr(stream)),
+          "ha_gather_wsum_u32keys")
+    return out
+
+
+def dedup_reduce_wbags(plan, bag_grads, weights, bag=None, bag_of=None, scale=1.0, out=None, stream=None):
+    """dedup_reduce on the pooled gradient bag_grads [B, width] of a weighted sum-pooled lookup (ha_dedup_reduce_wbags):
+    reduced[u,:] = the chain from +0 of fl(scale * fl(w_i * bag_grads[bag of i,:])) over unique key u's LIVE occurrences in
+    occurrence order -- bit for bit wbag_grad_rows followed by dedup_reduce(scale=).  The plan must be FINISHED (build(), or
+    sort() + finish()).  Give `bag` (fixed bags of that many ids) or `bag_of` (int32 [n], from ops.bag_of)."""
+    _require(bag_grads, torch.float32, "bag_grads")
+    if bag_grads.dim() != 2:
+        raise ValueError("bag_grads must be [B, width]")
+    if (bag is None) == (bag_of is None):
+        raise ValueError("give exactly one of bag and bag_of")
+    n, (nbags, width) = plan.n, bag_grads.shape
+    _weights_of(weights, n)
+    if bag_of is not None:
+        _require(bag_of, torch.int32, "bag_of")
+        if bag_of.numel() != n:
+            raise ValueError("bag_of must have one entry per planned id")
+    elif bag < 1 or n % bag or nbags != n // bag:
+        raise ValueError("bag_grads must be [n / bag, width]")
+    if out is None:
+        out = torch.empty((max(n, 1), width), dtype=torch.float32, device=bag_grads.device)
+    _require(out, torch.float32, "out")
+    if out.numel() < n * width:
+        raise ValueError("out must hold n rows")
+    check(_lib.load().ha_dedup_reduce_wbags(_ptr(plan.ws), n, _ptr(bag_grads), _ptr(weights), width,
+                                            int(bag) if bag is not None else 0, _ptr(bag_of) if bag_of is not None else None,
+                                            nbags, ctypes.c_float(scale), _ptr(out), _stream_ptr(stream)),
+          "ha_dedup_reduce_wbags")
+    return out
+
+
 # ---- weighted FM-pooled lookup (the second-order term of the FAE DeepFM, csrc/wfm.hip) ------------------------------------
 def embedding_lookup_wfm(table, ids, weights, offsets=None, sum_out=None, sq_out=None, stream=None):
     """Weighted FM-pooled lookup (ha_gather_wfm_*): per bag, over its LIVE occurrences in position order (weight not zero and id

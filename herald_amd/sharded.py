@@ -243,6 +243,22 @@ class HipEngine:
         return self.ops.dedup_reduce_bags(plan, bag_values, bag=bag, bag_of=bag_of, scale=scale, out=out,
                                           stream=self._stream())
 
+    # -- weighted bags: the two end kernels of pull_wsum / push_wbags (csrc/wshard.hip) --------------------------------------
+    def expand_wsum(self, rows, plan, weights, bag=None, offsets=None, out=None):
+        """out[b,:] = the chain from +0 of fl(w_i * rows[inverse[i],:]) over the LIVE positions of bag b in order (weight
+        not zero): expand followed by embedding_lookup_wsum over the row buffer, without the [n, width] rows."""
+        return self.ops.gather_wsum_u32keys(rows, plan.inverse(), weights.reshape(-1), bag=bag, offsets=offsets, out=out,
+                                            stream=self._stream())
+
+    def reduce_scaled_wbags(self, plan, bag_values, weights, scale, bag=None, bag_of=None, offsets=None):
+        """reduce_scaled on wbag_grad_rows(bag_values, weights) without that [n, width] tensor: position i contributes
+        fl(scale * fl(w_i * bag_values[its bag,:])) when w_i is not zero.  Bags as in reduce_scaled_bags."""
+        if offsets is not None:
+            bag_of = self.ops.bag_of(offsets, plan.n, stream=self._stream())
+        out = self._buf("reduced", max(plan.n, 1), bag_values.shape[1])
+        return self.ops.dedup_reduce_wbags(plan, bag_values, weights.reshape(-1), bag=bag, bag_of=bag_of, scale=scale,
+                                           out=out, stream=self._stream())
+
     def acc_apply(self, table, keys_i32, values):
         """table[key,:] = (table[key,:] + v_a) + v_b ... in the order the (key, value) pairs are listed."""
         n = keys_i32.numel()
@@ -1021,6 +1037,71 @@ class ShardedEmbedding:
         self._bag_layout("push_pull_bags (pull)", pull_ids, pull_offsets, None)
         self.push_bags(push_ids, bag_values, lr, offsets=push_offsets)
         return self.pull_sum(pull_ids, offsets=pull_offsets)
+
+    # -- weighted bags (embedding_lookup_op, mul_op by a 0/1 mask, reduce_sum_op(axes=1): the cold table of the FAE models) -----
+    # As the sum-pooled calls: routing, owner gather, exchanges, owner apply, `stats` and the Route are pull's / push's own --
+    # the ids are routed as they are, the padding id is one key --, and only this rank's two end kernels differ.  A dead
+    # occurrence (weight zero) takes no part.  Bit for bit pull + embedding_lookup_wsum over the rows / wbag_grad_rows + push.
+    def _check_weights(self, what, weights, shape):
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != self.table.device:
+            raise ValueError("%s: weights must be a float32 tensor on %s" % (what, self.table.device))
+        if tuple(weights.shape) != tuple(shape) or not weights.is_contiguous():
+            raise ValueError("%s: weights must be contiguous with the ids' shape %s, got %s"
+                             % (what, tuple(shape), tuple(weights.shape)))
+
+    def pull_wsum(self, ids=None, weights=None, offsets=None, route=None, return_route=False, out=None):
+        """out[b,:] = the chain from +0 of fl(w_i * table_global[id_i,:]) over bag b's LIVE occurrences (weight not zero) in
+        position order: pull followed by embedding_lookup_wsum over the pulled rows.  ids / offsets / route as pull_sum;
+        weights float32 on the store's device with the ids' shape.  Returns [B, width]."""
+        bag, nbags = self._bag_layout("pull_wsum", ids, offsets, route)
+        self._check_weights("pull_wsum", weights, tuple(ids.shape) if ids is not None else route.shape)
+        if out is not None and (tuple(out.shape) != (nbags, self.width) or out.dtype != torch.float32 or
+                                not out.is_contiguous()):
+            raise ValueError("pull_wsum: out must be contiguous float32 [%d, %d]" % (nbags, self.width))
+        eng = self.engine
+        if route is None:
+            route = self.prefetch(ids)
+        r = self.complete(route)
+        eng.wait_event(r.ready)
+        rows_send = eng.gather_keys(self.table, r.keys_recv, scratch="pull_send")
+        rows_recv = eng.rows_buffer("pull_recv", r.u, self.width)
+        self._a2a(rows_recv, rows_send, r.send_cnt, r.recv_cnt)
+        out = eng.expand_wsum(rows_recv, r.plan, weights, bag=bag, offsets=offsets, out=out)
+        self._account(r.send_cnt, r.recv_cnt, 4, 4 * self.width)
+        self._release(r)
+        return (out, r) if return_route else out
+
+    def push_wbags(self, ids, bag_values, weights, lr=None, offsets=None, route=None):
+        """push of the pooled values bag_values [B, width] of a weighted lookup: every live id of bag b pushes
+        fl(-lr * fl(w_i * bag_values[b,:])) (scale 1 if lr is None) -- push(ids, wbag_grad_rows(bag_values, weights), lr)
+        without the [n, width] values."""
+        bag, nbags = self._bag_layout("push_wbags", ids, offsets, route)
+        self._check_bag_values("push_wbags", bag_values, nbags)
+        self._check_weights("push_wbags", weights, tuple(ids.shape) if ids is not None else route.shape)
+        eng = self.engine
+        if route is None:
+            route = self.prefetch(ids)
+        r = self.complete(route)
+        scale = 1.0 if lr is None else -float(lr)
+        eng.wait_event(r.ready)   # the plan and the keys were produced on the side stream
+        reduced = eng.reduce_scaled_wbags(r.plan, bag_values.contiguous(), weights, scale, bag=bag, offsets=offsets)
+        rows_send = reduced[:r.u]
+        rows_recv = eng.rows_buffer("push_recv", sum(r.recv_cnt), self.width)
+        self._a2a(rows_recv, rows_send, r.recv_cnt, r.send_cnt)
+        eng.acc_apply(self.table, r.keys_recv, rows_recv)
+        self._account(r.send_cnt, r.recv_cnt, 4 * self.width, 0)
+        self._release(r)
+
+    def push_pull_wbags(self, push_ids, bag_values, push_weights, lr, pull_ids, pull_weights, push_offsets=None,
+                        pull_offsets=None):
+        """push_wbags of this batch, then pull_wsum of the next one (SSPushPull on weighted pooled access)."""
+        _, nbags = self._bag_layout("push_pull_wbags (push)", push_ids, push_offsets, None)
+        self._check_bag_values("push_pull_wbags", bag_values, nbags)
+        self._check_weights("push_pull_wbags (push)", push_weights, tuple(push_ids.shape))
+        self._bag_layout("push_pull_wbags (pull)", pull_ids, pull_offsets, None)
+        self._check_weights("push_pull_wbags (pull)", pull_weights, tuple(pull_ids.shape))
+        self.push_wbags(push_ids, bag_values, push_weights, lr, offsets=push_offsets)
+        return self.pull_wsum(pull_ids, pull_weights, offsets=pull_offsets)
 
     # -- checkpoint format of the reference: raw fp32 `<name>_<part>.dat` per shard ------------------------
     CKPT_CHUNK_BYTES = 64 << 20

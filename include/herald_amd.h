@@ -1558,6 +1558,33 @@ int ha_sgd_sparse_update_wbags_f32ids(float *table, int64_t rows, int64_t width,
 int ha_sgd_sparse_update_wbags_u64ids(float *table, int64_t rows, int64_t width, const uint64_t *ids, const float *weights,
                                       int64_t n, const float *bag_grads, int64_t bag, const int64_t *offsets, int64_t nbags,
                                       float lr, ha_stream_t stream);
+/* ---- weighted bags on the row-sharded table: the end kernels of pull_wsum / push_wbags (csrc/wshard.hip) ----------------
+ * The FAE models keep their cold table behind the parameter server (fae_wdl_criteo.py: ctx=ht.cpu(0)); herald_amd/sharded.py
+ * serves it with the routing, exchanges and owner apply of pull / push and these two kernels at this rank's ends.
+ * The weighted forward with the rows named by uint32 keys (device uint32[n]) into a buffer of rows: the contract of
+ * ha_gather_wsum_f32ids to the letter -- weights float32[n] in position order, an occurrence is live when its weight is not zero
+ * and its key is below rows, per bag and column over the live occurrences in position order acc = +0; acc = fl(acc + fl(w * r)),
+ * nothing contracted, clamped offsets, the same slice rule.  All weights 1.0f: ha_gather_sum_u32keys bit for bit.  rows_buf is
+ * the [u, width] buffer of the unique rows a batch received and keys its plan's inverse[n].  n > 0 requires rows >= 1 (the
+ * kernel loads row 0 for a dead occurrence); checked, as everything else, before any device access. */
+int ha_gather_wsum_u32keys(const float *rows_buf, int64_t rows, int64_t width, const uint32_t *keys, const float *weights,
+                           int64_t n, int64_t bag, const int64_t *offsets, int64_t nbags, float *out, ha_stream_t stream);
+/* The worker side of a PS sparse push of weighted pooled slices: for every unique key u of a FINISHED plan (ha_plan_build_*,
+ * ha_plan_sort_* + ha_plan_finish; what ha_shard_route_pack_* builds), over its occurrences i0 < i1 < ... in ascending order,
+ *   acc = +0;  acc = fl(acc + fl(scale * fl(w_i * bag_grads[bag(i),:])))      three roundings per element
+ * An occurrence whose weight is zero takes no part and its bag's gradient row is not read; a key without live occurrence gets
+ * a +0.0f row.  Keys are not tested against a row count.  reduced holds n rows, the first n_unique are written.  Exactly one of
+ * bag >= 1 (fixed bags, bag_of NULL, n == nbags * bag) and bag_of (int32[n] from ha_bag_of, bag == 0), as ha_dedup_reduce_bags;
+ * an entry of bag_of beyond nbags - 1 is clamped to it, as ha_wbag_grad_rows clamps it.  width % 4 == 0 with 16-byte aligned
+ * bag_grads / reduced takes the 16-byte path, anything else the scalar one.  reduced must alias neither input.
+ * Bit for bit, with no corner case, ha_wbag_grad_rows into an [n, width] tensor followed by ha_dedup_reduce_scaled: that
+ * sequence gives a dead occurrence the term fl(scale * +0) = +-0, and a chain that starts at +0 never holds -0, so the term
+ * changes no bit.  Tolerance mode 1 or 2: the entry point runs exactly that composed sequence through the library's per-stream
+ * scratch (n * width floats); plan_ws, bag_of, bag_grads, weights and reduced must then be the caller's own allocations (see
+ * ha_dedup_reduce_bags).  The plan's scratch words (header word 0, the radix scratch) are rewritten, as by ha_sgd_apply_wbags.
+ * Every argument check precedes any device access; n == 0 returns 0. */
+int ha_dedup_reduce_wbags(const void *plan_ws, int64_t n, const float *bag_grads, const float *weights, int64_t width,
+                          int64_t bag, const int32_t *bag_of, int64_t nbags, float scale, float *reduced, ha_stream_t stream);
 /* ---- weighted FM-pooled lookup: the second-order term of the FAE DeepFM (csrc/wfm.hip) ----------------------------------
  * examples/ctr/models/fae_deepfm_avazu.py:43-80: the cold rows are multiplied by the 0/1 mask and consumed as
  * reduce_sum_op(x, axes=1) and as reduce_sum_op(mul_op(x, x), axes=1); the square of the sum is taken only after the hot
