@@ -61,7 +61,10 @@ libherald_amd.so, in the three placements the reference's run_hetu.py offers:
                      sum: torch's embedding_bag with per-sample weights), every other id by the main table through the WEIGHTED
                      sum-pooled lookup (ha_gather_wsum_*: the slot of a hot id is the padding id 0 with weight 0) and, with
                      --optimizer sgd, the fused weighted apply (ha_sgd_sparse_update_wbags_*: the dead slots leave the plan as
-                     one out-of-range key); the other optimizers take the weighted gradient expanded.  --embedding hbm only.
+                     one out-of-range key); the other optimizers take the weighted gradient expanded.  --embedding hbm; --embedding ps
+                     with --ps-fuse-wbags; --embedding cache with --cache-planned --bsp 0 --cache-fuse-wbags (the reference's
+                     hybrid_fae_wdl_criteo.sh: the cold table behind the HET cache, ha_cache_lookup_wsum_planned /
+                     ha_cache_update_planned_wbags).
   --model fae_deepfm the FAE DeepFM (examples/ctr/models/fae_deepfm_avazu.py; also fae_deepfm_avazu, fae_dfm_avazu): fae_wdl's hot
                      list and split over the DeepFM's two tables.  The first-order table is the weighted bag at width 1; the
                      second-order table goes through the WEIGHTED FM-pooled lookup (ha_gather_wfm_*: S and Q of the cold rows,
@@ -534,7 +537,7 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
           cache_limit=None, seed=0, device="cuda:0", table_init=None, log_every=0, model="wdl", a2a=None, allreduce=None,
           bsp=0, cache_perf=False, perf_csv_dir=None, cache_planned=False, cache_fuse_bags=True, optimizer="sgd",
           opt_fuse_bags=True, ps_fuse_bags=True, cache_fuse_bag_calls=False, first_order_init=None, fae_hot_rate=0.01,
-          ps_fuse_wbags=False):
+          ps_fuse_wbags=False, cache_fuse_wbags=False):
     """Runs `steps` training steps; returns (losses, embedding parameter, tower).  cache_planned (--cache-planned, with
     --embedding cache on one rank): the cache's planned flow -- the loader's ring hands the communicate op the ids one
     batch further ahead (`peek_ids`), the bookkeeping of batch k + 1 runs beside the step on batch k.  At bsp 0 these are the
@@ -564,6 +567,10 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     With ps_fuse_wbags on --embedding ps the cold table lives behind the sharded store, as the reference keeps it on ctx=ht.cpu(0):
     the communicate op is given the COLD ids and the cold mask of batch k + 1 and bag=26, pulls weighted pooled rows
     (store.pull_wsum) and pushes the weighted pooled slices as they are (push_wbags): no [batch * 26, width] tensor either way.
+    With cache_fuse_wbags (--cache-fuse-wbags) on --embedding cache with cache_planned at bsp 0 on one rank the cold table lives
+    behind the HET cache -- the reference's hybrid_fae_wdl_criteo.sh, --cache lfu --bound 0 --bsp 0 --: the op pulls with
+    embedding_lookup_wsum_planned and pushes with embedding_update_planned_wbags, the bookkeeping of batch k + 1 beside step k.
+    Every other fae_wdl run on the cache is refused.
     model="fae_deepfm" (--model fae_deepfm), --embedding hbm with --optimizer sgd only (train_fae_deepfm): the FAE split over the
     DeepFM's two tables, the second-order one through the weighted FM-pooled lookup and its fused apply."""
     if model in FAE_FM_MODELS:
@@ -582,10 +589,14 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
     dev = torch.device(device)
     pooled = model in POOLED_MODELS
     fae = model in FAE_MODELS
-    if fae and not (embedding == "hbm" or (embedding == "ps" and ps_fuse_wbags)):
-        raise ValueError("%s runs with --embedding hbm, or with --embedding ps and --ps-fuse-wbags (ps_fuse_wbags=True): the "
-                         "weighted sum-pooled lookup has no form on the step engines and no pooled form on the cache tiers (got "
-                         "--embedding %s)" % (model, embedding))
+    import torch.distributed as dist
+    fae_on_cache = embedding == "cache" and cache_fuse_wbags and cache_planned and bsp == 0 and \
+        not (dist.is_initialized() and dist.get_world_size() > 1)
+    if fae and not (embedding == "hbm" or (embedding == "ps" and ps_fuse_wbags) or fae_on_cache):
+        raise ValueError("%s runs with --embedding hbm, with --embedding ps and --ps-fuse-wbags (ps_fuse_wbags=True), or with "
+                         "--embedding cache, --cache-planned, --bsp 0 and --cache-fuse-wbags (cache_fuse_wbags=True) on one rank: "
+                         "the weighted sum-pooled lookup has no form on the step engines and no pooled form in the other cache "
+                         "flows (got --embedding %s)" % (model, embedding))
     if optimizer not in OPTIMIZERS:
         raise ValueError("optimizer must be one of %s, got %r" % (", ".join(OPTIMIZERS), optimizer))
     if optimizer != "sgd" and embedding != "hbm":
@@ -631,10 +642,11 @@ def train(embedding="hbm", rows=200000, width=32, batch=256, steps=50, lr=0.01, 
                                  max(rows // 10, batch * NFIELD * (2 if cache_planned and bsp < 0 else 1)),
                                  cache_perf_enable=cache_perf, cache_plan_ahead=cache_planned, cache_fuse_bags=cache_fuse_bags,
                                  ps_fuse_bags=ps_fuse_bags, cache_fuse_bag_calls=cache_fuse_bag_calls,
-                                 ps_fuse_wbags=ps_fuse_wbags)
+                                 ps_fuse_wbags=ps_fuse_wbags, cache_fuse_wbags=cache_fuse_wbags)
         barrier = dist.barrier if world > 1 else (lambda: None)
         if fae:
-            # the cold table behind the store: the op pulls and pushes the COLD ids with their mask, weighted and pooled
+            # the cold table behind the store (--embedding ps) or behind the cache over it (--embedding cache, the planned pairs):
+            # the op pulls and pushes the COLD ids with their mask, weighted and pooled
             def cold_of(k, what):
                 return splits[k % len(splits)][what]
             comm = hetu_ops.ParameterServerCommunicateOp(param, lr, next_ids=lambda: cold_of(state["k"] + 1, 1),
@@ -836,6 +848,10 @@ def main():
     ap.add_argument("--no-ps-fuse-bags", action="store_true",
                     help="--embedding ps with --model emb_sum_wdl: pull per-occurrence rows and push the expanded gradient "
                          "instead of the store's pooled pull_sum / push_bags (the same bits)")
+    ap.add_argument("--cache-fuse-wbags", action="store_true",
+                    help="--embedding cache --cache-planned --bsp 0 with --model fae_wdl: the cold table behind the HET cache -- the "
+                         "communicate op pulls weighted pooled rows (embedding_lookup_wsum_planned) and pushes the weighted pooled "
+                         "slices as they are (embedding_update_planned_wbags)")
     ap.add_argument("--ps-fuse-wbags", action="store_true",
                     help="--embedding ps with --model fae_wdl: the cold table behind the sharded store -- the communicate op "
                          "pulls weighted pooled rows (pull_wsum) and pushes the weighted pooled gradient as it is (push_wbags), "
@@ -877,8 +893,12 @@ def main():
         ap.error("--optimizer %s is applied to the embedding table on --embedding hbm only" % args.optimizer)
     if model in FM_MODELS + FAE_FM_MODELS and (args.laia or args.embedding != "hbm" or args.optimizer != "sgd"):
         ap.error("--model %s runs with --embedding hbm and --optimizer sgd only" % model)
-    if model in FAE_MODELS and (args.laia or not (args.embedding == "hbm" or (args.embedding == "ps" and args.ps_fuse_wbags))):
-        ap.error("--model %s runs with --embedding hbm, or with --embedding ps and --ps-fuse-wbags" % model)
+    if args.cache_fuse_wbags and not (args.embedding == "cache" and args.cache_planned and args.bsp == 0):
+        ap.error("--cache-fuse-wbags needs --embedding cache, --cache-planned and --bsp 0 (the planned lookup + update pairs)")
+    if model in FAE_MODELS and (args.laia or not (args.embedding == "hbm" or (args.embedding == "ps" and args.ps_fuse_wbags) or
+                                                  (args.embedding == "cache" and args.cache_fuse_wbags))):
+        ap.error("--model %s runs with --embedding hbm, with --embedding ps and --ps-fuse-wbags, or with --embedding cache, "
+                 "--cache-planned, --bsp 0 and --cache-fuse-wbags" % model)
     if args.nepoch > 0:
         args.steps *= args.nepoch
     cache_limit = max(int(args.cache_limit_ratio * args.rows), args.batch * NFIELD)
@@ -897,7 +917,8 @@ def main():
                        log_every=max(1, args.steps // 10), model=args.model, bsp=args.bsp if comm is not None else 0,
                        cache_perf=args.cache_perf, cache_planned=args.cache_planned, optimizer=args.optimizer,
                        ps_fuse_bags=not args.no_ps_fuse_bags, cache_fuse_bag_calls=args.cache_fuse_bag_calls,
-                       fae_hot_rate=args.fae_hot_rate, ps_fuse_wbags=args.ps_fuse_wbags)[0]
+                       fae_hot_rate=args.fae_hot_rate, ps_fuse_wbags=args.ps_fuse_wbags,
+                       cache_fuse_wbags=args.cache_fuse_wbags)[0]
     if local_rank == 0:
         print("first 10 steps: loss %.5f   last 10 steps: loss %.5f" % (np.mean(losses[:10]), np.mean(losses[-10:])))
 

@@ -316,6 +316,9 @@ def _declare(L):
         "ha_cache_lookup_sum_planned": [vp, i64, i64, i64, vp, vp, vp],
         "ha_cache_update_planned_bags": [vp, i64, vp, i64, i64, vp, vp],
         "ha_cache_run_planned_pairs_bags": [vp, c.c_int, i64, i64, i64, vp, vp, vp],
+        "ha_cache_lookup_wsum_planned": [vp, i64, i64, i64, vp, vp, vp, vp],
+        "ha_cache_update_planned_wbags": [vp, i64, vp, vp, c.c_float, i64, i64, vp, vp],
+        "ha_cache_run_planned_pairs_wbags": [vp, c.c_int, i64, i64, i64, vp, vp, vp, c.c_float, vp],
         "ha_cache_plan_block_push_pull": [vp, vp, c.c_int, vp, c.c_int, vp, vp],
         "ha_cache_push_pull_planned": [vp, i64, vp, i64, vp, vp],
         "ha_cache_run_planned_push_pulls": [vp, c.c_int, vp, vp, vp, vp, vp],

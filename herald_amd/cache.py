@@ -23,6 +23,7 @@ and ids >= length) are undefined behaviour in this tier; replace padding ids bef
 conversion is the library's one rule (f32_to_key), so -0.0 and -0.99 are key 0 here as everywhere.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -823,6 +824,94 @@ class _CacheBase:
               "ha_cache_run_planned_pairs_bags")
         del pl[:cnt]
 
+    # ---- weighted bags in the planned pairs (the FAE models' masked bags): the bookkeeping never looks at a weight -------------
+    @staticmethod
+    def _weights_arg(who, what, w, n):
+        """Checks of a weights argument, before anything native: a contiguous float32 device tensor of n elements."""
+        if not torch.is_tensor(w):
+            raise TypeError("%s: %s must be a tensor" % (who, what))
+        if w.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32 (got %s)" % (who, what, w.dtype))
+        if not (w.is_cuda and w.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous device tensor" % (who, what))
+        if w.numel() != n:
+            raise ValueError("%s: %s has %d elements, the planned batch %d ids" % (who, what, w.numel(), n))
+
+    def embedding_lookup_wsum_planned(self, out, weights, bag=None, offsets=None):
+        """The lookup of the next planned batch, delivered as WEIGHTED sums of its bags (ha_cache_lookup_wsum_planned), ONE
+        launch: out[b,:] = +0, then + fl(w_j * r_j) over the bag's occurrences with w_j != 0 in position order -- bit for bit
+        embedding_lookup_planned followed by ops.embedding_lookup_wsum over the rows; the cache is left as that lookup leaves
+        it, whatever the weights (a dead head occurrence still refreshes its line).  weights: float32 device tensor of n
+        elements ([nbags, bag] or [n]); out, bag, offsets: as embedding_lookup_sum_planned."""
+        who = "embedding_lookup_wsum_planned"
+        k = self._pooled_due(who, True)
+        nbags = self._pooled_args(who, "out", out, k.numel(), bag, offsets, "offsets")
+        self._weights_arg(who, "weights", weights, k.numel())
+        s = self._stream()
+        check(self._L.ha_cache_lookup_wsum_planned(self._h, k.numel(), nbags, int(bag) if bag is not None else 0,
+                                                   ctypes.c_void_p(offsets.data_ptr() if offsets is not None else None),
+                                                   ctypes.c_void_p(weights.data_ptr() if k.numel() else None),
+                                                   ctypes.c_void_p(out.data_ptr() if nbags else None),
+                                                   ctypes.c_void_p(s.cuda_stream)), "ha_cache_lookup_wsum_planned")
+        self._planned[0][1] = True
+        if self.perf_enabled:
+            self._perf_record(0)
+        return Wait(s, [k, out, offsets, weights]) if self._planned_waits else None
+
+    def embedding_update_planned_wbags(self, bag_grads, weights, bag=None, bag_of=None, scale=1.0):
+        """The update of the planned batch whose lookup was the last planned call, from the pooled gradient bag_grads [nbags,
+        width] of WEIGHTED bags (ha_cache_update_planned_wbags), ONE launch: bit for bit
+        embedding_update_planned(ops.wbag_grad_rows(bag_grads, ..., weights) * scale) -- occurrence i contributes
+        fl(scale * fl(w_i * bag_grads[bag(i)])) when w_i != 0 and fl(scale * +0) otherwise.  scale must be finite."""
+        who = "embedding_update_planned_wbags"
+        k = self._pooled_due(who, False)
+        nbags = self._pooled_args(who, "bag_grads", bag_grads, k.numel(), bag, bag_of, "bag_of")
+        self._weights_arg(who, "weights", weights, k.numel())
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError("%s: scale must be finite (got %r)" % (who, scale))
+        s = self._stream()
+        check(self._L.ha_cache_update_planned_wbags(self._h, k.numel(), ctypes.c_void_p(bag_grads.data_ptr() if nbags else None),
+                                                    ctypes.c_void_p(weights.data_ptr() if k.numel() else None), scale,
+                                                    nbags, int(bag) if bag is not None else 0,
+                                                    ctypes.c_void_p(bag_of.data_ptr() if bag_of is not None else None),
+                                                    ctypes.c_void_p(s.cuda_stream)), "ha_cache_update_planned_wbags")
+        self._planned.pop(0)
+        if self.perf_enabled:
+            self._perf_record(1)
+        return Wait(s, [k, bag_grads, bag_of, weights]) if self._planned_waits else None
+
+    def run_planned_pairs_wbags(self, outs, bag_grads, weights, bag, scale=1.0):
+        """The next len(outs) planned pairs by ONE library call (ha_cache_run_planned_pairs_wbags), weighted both ways with fixed
+        bags of `bag` ids: embedding_lookup_wsum_planned(outs[k], weights[k], bag) then
+        embedding_update_planned_wbags(bag_grads[k], weights[k], bag, scale=scale).  Every pair has the same number of ids.  For
+        callers that have the pairs' buffers at hand (a benchmark loop); no perf records."""
+        who = "run_planned_pairs_wbags"
+        cnt = len(outs)
+        pl = getattr(self, "_planned", None) or []
+        if getattr(self, "_chain", None) or cnt > len(pl) or len(bag_grads) != cnt or len(weights) != cnt or (pl and pl[0][1]):
+            raise ValueError("%s: %d pairs, %d planned" % (who, cnt, len(pl)))
+        if cnt == 0:
+            return
+        n = pl[0][0].numel()
+        if any(pl[k][0].numel() != n for k in range(cnt)):
+            raise ValueError("%s: the pairs of one call have the same number of ids" % who)
+        nbags = {self._pooled_args(who, "outs[%d]" % k, outs[k], n, bag, None, "offsets") for k in range(cnt)} | \
+                {self._pooled_args(who, "bag_grads[%d]" % k, bag_grads[k], n, bag, None, "bag_of") for k in range(cnt)}
+        nbags = nbags.pop()
+        for k in range(cnt):
+            self._weights_arg(who, "weights[%d]" % k, weights[k], n)
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError("%s: scale must be finite (got %r)" % (who, scale))
+        s = self._stream()
+        op = (ctypes.c_void_p * cnt)(*[o.data_ptr() if nbags else None for o in outs])
+        gp = (ctypes.c_void_p * cnt)(*[g.data_ptr() if nbags else None for g in bag_grads])
+        wp = (ctypes.c_void_p * cnt)(*[w.data_ptr() if n else None for w in weights])
+        check(self._L.ha_cache_run_planned_pairs_wbags(self._h, cnt, n, nbags, int(bag), op, gp, wp, scale,
+                                                       ctypes.c_void_p(s.cuda_stream)), "ha_cache_run_planned_pairs_wbags")
+        del pl[:cnt]
+
     # ---- the entries of a push-pull chain, sum-pooled on both sides ---------------------------------------------------------
     def _chain_bags_args(self, who, j, out, bag_grads, bag, pull_offsets, push_bag_of):
         """Entry j of the chain list, checked for a pooled call before anything native -> (kind, pull keys, push keys,
@@ -1399,6 +1488,17 @@ class CacheSparseTable:
 
     def run_planned_pairs_bags(self, outs, bag_grads, bag):
         self.cache.run_planned_pairs_bags(outs, bag_grads, bag)
+
+    def embedding_lookup_wsum_planned(self, out, weights, bag=None, offsets=None, sync=False):
+        w = self.cache.embedding_lookup_wsum_planned(out, weights, bag=bag, offsets=offsets)
+        return self._finish(w, sync) if w is not None else None
+
+    def embedding_update_planned_wbags(self, bag_grads, weights, bag=None, bag_of=None, scale=1.0, sync=False):
+        w = self.cache.embedding_update_planned_wbags(bag_grads, weights, bag=bag, bag_of=bag_of, scale=scale)
+        return self._finish(w, sync) if w is not None else None
+
+    def run_planned_pairs_wbags(self, outs, bag_grads, weights, bag, scale=1.0):
+        self.cache.run_planned_pairs_wbags(outs, bag_grads, weights, bag, scale=scale)
 
     def looked_up_last(self, keys):
         """True when `keys` is the device tensor the cache's last operation, an embedding_lookup, was given (same storage,

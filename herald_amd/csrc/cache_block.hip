@@ -39,6 +39,7 @@
 // MI355X_MICROARCH.md "inter-workgroup visibility"); the row launches own data, grad, hasgrad, a line's version, the store's
 // rows and versions, and read nothing the bookkeeping writes except the items.  The call-by-call entry points are refused
 // until the planned batches are consumed.
+#include <cmath>
 #include "cache_dev.h"
 #include "scatter_dev.h"
 
@@ -1149,12 +1150,18 @@ struct SumPlan {
 };
 constexpr int kSumWaves = 4;     // waves per workgroup
 // row-pointer flags of a lane's occurrence
-constexpr int kSumOk = 1, kSumGrad = 2, kSumHead = 4;
+constexpr int kSumOk = 1, kSumGrad = 2, kSumHead = 4, kSumLive = 8;
 
-template <int VEC, int ROWS, bool PP = false>
+// WEIGHTED (ha_cache_lookup_wsum_planned, the FAE models' masked bags): occurrence j adds fl(w_j * r_j) when w_j != 0 (+-0 are
+// zero, NaN is not) and nothing otherwise.  The weight of position l comes with inverse[j] in the first round trip and is
+// broadcast as bits beside the row's flag word, where the live bit (kSumLive) lies.  Everything in front of the multiply --
+// the pull decision, Line::addup, the head's refreshed data row and staged version -- works on the UNWEIGHTED row and does not
+// look at the weight: a dead head occurrence refreshes its line as a live one does, so the cache is left as the unpooled
+// lookup leaves it.  WEIGHTED = false reads no weight and compiles to what it was.
+template <int VEC, int ROWS, bool PP = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_kernel(
     Cache c, SumPlan sp, long long n, long long bag, const int64_t *__restrict__ offsets, long long nbags, uint32_t nslice,
-    float *__restrict__ out) {
+    float *__restrict__ out, const float *__restrict__ weights) {
     typedef typename SumVec<VEC>::T V;
     typedef const V __attribute__((address_space(1))) *GlobalV;
     const int lane = lane_id();
@@ -1187,6 +1194,9 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
         const long long j = j0 + (mine ? lane : cnt - 1);                          // lo <= j < hi <= n
         // ---- the occurrence's item (every index is checked before an address is formed from it)
         const int u = sp.inverse[j];
+        int wbits = 0;
+        if (WEIGHTED)
+            wbits = __float_as_int(weights[j]);      // (weights: n floats)
         const bool u_ok = u >= 0 && u < n;
         const int uu = u_ok ? u : 0;
         int s = sp.it_slot[uu];
@@ -1236,7 +1246,8 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
         const int src_lo = static_cast<int>(static_cast<uint32_t>(sa)), src_hi = static_cast<int>(static_cast<uint32_t>(sa >> 32));
         const int lof_lo = static_cast<int>(static_cast<uint32_t>(loff)), lof_hi = static_cast<int>(static_cast<uint32_t>(loff >> 32));
         // the line has a gradient buffer: Line::addup() re-adds it to the pulled row
-        const int rf = (ok ? kSumOk : 0) | ((ok && pull && (fl & kPosInit)) ? kSumGrad : 0) | ((head && pull) ? kSumHead : 0);
+        const int rf = (ok ? kSumOk : 0) | ((ok && pull && (fl & kPosInit)) ? kSumGrad : 0) | ((head && pull) ? kSumHead : 0) |
+                       ((WEIGHTED && (wbits & 0x7FFFFFFF) != 0) ? kSumLive : 0);
         for (int r0 = 0; r0 < cnt; r0 += ROWS) {
             V x[ROWS];
 #pragma unroll
@@ -1267,11 +1278,23 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
                         *reinterpret_cast<V *>(c.data + o + col) = xv;
                 }
                 const bool rok = (f & kSumOk) != 0;
+                if (WEIGHTED) {
+                    // (an item without a line is the zero row the unpooled lookup writes: w * 0)
+                    const float w = __int_as_float(__builtin_amdgcn_readlane(wbits, in ? r0 + t : 0));      // wave-uniform
+                    const bool take = in && (f & kSumLive) != 0;                                            // wave-uniform
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    const float a = SumVec<VEC>::get(acc, k);
-                    const float sum = __fadd_rn(a, rok ? SumVec<VEC>::get(xv, k) : 0.f);
-                    SumVec<VEC>::set(acc, k, in ? sum : a);
+                    for (int k = 0; k < VEC; ++k) {
+                        const float a = SumVec<VEC>::get(acc, k);
+                        const float sum = __fadd_rn(a, __fmul_rn(w, rok ? SumVec<VEC>::get(xv, k) : 0.f));
+                        SumVec<VEC>::set(acc, k, take ? sum : a);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) {
+                        const float a = SumVec<VEC>::get(acc, k);
+                        const float sum = __fadd_rn(a, rok ? SumVec<VEC>::get(xv, k) : 0.f);
+                        SumVec<VEC>::set(acc, k, in ? sum : a);
+                    }
                 }
             }
         }
@@ -1279,6 +1302,201 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
     // the pooled rows are consumed by another kernel (the dense tower): written around the L2, as bag_sum_kernel's
     if (live)
         __builtin_nontemporal_store(acc, reinterpret_cast<V *>(out + static_cast<uint64_t>(b) * width + col));
+}
+
+// ---- the update of a planned batch from WEIGHTED bags (ha_cache_update_planned_wbags, the FAE models' masked bags) -----------
+// The accumulate role of the launch below in its WEIGHTED form.  The term of occurrence i is
+// t_i = fl(scale * fl(w_i * g[bag(i), :])) when w_i != 0 and z = fl(scale * +0) otherwise: ha_cache_update_planned on the
+// [n, width] tensor of the t_i, bit for bit.  A key's chain is acc = acc - fl(-1 * t_i) over its occurrences in position
+// order (step<kModeSgd> with lr = -1, what apply_body runs),
+// into the line's gradient buffer (from +0 without kPosInit) and into its data row; the push epilogue and the stores are
+// apply_body's.  The dead occurrences are NOT walked: adding z = -0 changes nothing, adding z = +0 changes only a -0
+// accumulator, and after the first +0 term the accumulator is never -0 again (round-to-nearest gives -0 only from -0 + -0), so
+// the chain over all occurrences is the chain over the live ones followed by ONE add of z whenever the run holds a dead
+// occurrence (tests/test_wcache_cpu.py).  No gradient row of a dead occurrence is read: what it holds cannot reach the cache.
+//
+// MI355X layout: a wave per sorted position, as apply_body.  The wave at offset o < W = min(run length, slices, 16) of its run
+// takes the column slices o, o + W, ... (64 * VEC columns each); every other wave leaves after its window.  It walks the run
+// from its first position: the window of sorted positions p-16 .. p+47 holds a run shorter than 48 whole (the common case:
+// perm and the weights are two round trips), a longer run goes on in blocks of kWcacheTrip * 64 positions, sorted and perm
+// of the next block requested before this block's weights are used.  Lane l holds bag and weight of one position; the live
+// ones are walked by the bits of one ballot (scalar), kBatch gradient rows in flight before the first multiply -- a dead
+// occurrence costs neither a row load nor a chain step, and the padding id's all-dead run of thousands is one scan of its
+// weights and one add of z.  No LDS, no barrier.
+constexpr int kWcacheTrip = 4;
+struct WbagArgs {
+    const float *weights;      // [n]
+    float scale;
+    uint32_t nbags;
+};
+// the accumulate role of cache_update_planned_kernel<VEC, true, true>; vblock: the workgroup's index among the role's
+template <int VEC>
+__device__ __forceinline__ void cache_wbags_accumulate(const Cache &c, const uint32_t *__restrict__ sorted,
+                                                       const int32_t *__restrict__ perm, int n,
+                                                       const float *__restrict__ bag_grads, const ApplyMaps &maps,
+                                                       const WbagArgs &wa, int vblock) {
+    const float *__restrict__ weights = wa.weights;
+    const float scale = wa.scale;
+    const uint32_t nbags = wa.nbags;
+    constexpr int kBatch = VEC == 4 ? 8 : 16;
+    const int lane = lane_id();
+    const int w = uniform(static_cast<int>(threadIdx.x >> 6));
+    const int p = vblock * kPosPerBlock + w;
+    if (p >= n)
+        return;
+    const int width = static_cast<int>(c.width);
+    // ---- the window p-16 .. p+47: the wave's offset in its run, the run's end if it lies inside
+    const int q = p - kLookBack + lane;
+    const int cq = max(0, min(q, n - 1));
+    const uint32_t ks = sorted[cq];
+    const int pi0 = perm[cq];
+    const int4 pit = maps.pos_item[p];
+    const uint32_t key = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ks), kLookBack));
+    const unsigned long long eq = __ballot(q >= 0 && q < n && ks == key);
+    const uint32_t inv_lo = static_cast<uint32_t>(~eq) & 0xFFFFu;
+    const int o = inv_lo == 0 ? kLookBack : (__builtin_clz(inv_lo) - 16);      // offset in the run, capped
+    const unsigned long long inv_hi = (~eq) >> kLookBack;                      // bit t <-> position p+t, 48 valid bits
+    const int fwd = __builtin_ctzll(inv_hi | (1ull << 48));                    // 1..48 (48: the run reaches the window's end)
+    const int nslice = (width + kWave * VEC - 1) / (kWave * VEC);
+    const int workers = min(min(o + fwd, nslice), kLookBack);
+    if (o >= workers)
+        return;
+    if (pit.x < 0 || pit.x >= c.S)
+        return;      // a key without a line / a record out of range: ignored, as apply_body does
+    const uint64_t row = static_cast<uint64_t>(pit.x);
+    const bool init = (pit.z & kPosInit) != 0;
+    float *dst_row = c.grad + row * static_cast<uint64_t>(width);
+    const bool d2on = (pit.z & kPosTemp) == 0;
+    float *d2row = maps.dst2 + row * static_cast<uint64_t>(width);
+    float *push = ((pit.z & kPosPush) && static_cast<uint64_t>(static_cast<uint32_t>(pit.y)) < maps.push_rows)
+                      ? maps.push_tab + static_cast<uint64_t>(static_cast<uint32_t>(pit.y)) * static_cast<uint64_t>(width)
+                      : nullptr;
+    const float *push2 = (pit.z & kPosVictimPush)
+                             ? c.grad + static_cast<uint64_t>(*maps.victim_row) * static_cast<uint64_t>(width)
+                             : nullptr;
+    const bool keep = (pit.z & kPosKeep) != 0;
+    const float z = __fmul_rn(scale, 0.f);
+    // bag of occurrence i, clamped as wbag_grad_rows_kernel clamps it: no row beyond bag_grads is read whatever bag_of holds
+    auto bag_at = [&](int i) {
+        const uint32_t b = static_cast<uint32_t>(maps.valmap ? maps.valmap[i] : bag_row(i, maps.valdiv));
+        return static_cast<int>(b < nbags ? b : nbags - 1);
+    };
+    // the window's share of the run: lanes kLookBack - o .. kLookBack + fwd - 1
+    const int bg0 = bag_at(pi0);
+    const int wb0 = __float_as_int(weights[pi0]);      // (pi0 < n whatever the lane's position: weights has n elements)
+    const bool in0 = lane >= kLookBack - o && lane < kLookBack + fwd;
+    const unsigned long long live0 = __ballot(in0 && (wb0 & 0x7FFFFFFF) != 0);
+    const bool dead0 = __ballot(in0 && (wb0 & 0x7FFFFFFF) == 0) != 0ull;
+
+    for (int sl = o; sl < nslice; sl += workers) {
+        const int col = (sl * kWave + lane) * VEC;
+        const bool colok = col < width;      // (VEC > 1: width % VEC == 0)
+        const int colc = colok ? col : 0;
+        Vec<VEC> acc, acc2;
+        acc.zero();
+        acc2.zero();
+        if (init)
+            acc.load(dst_row + colc);
+        if (d2on)
+            acc2.load(d2row + colc);
+        // the live occurrences of one block of 64 positions, in position order
+        auto chain = [&](unsigned long long m, int bg, int wb) {
+            while (m != 0ull) {
+                int tt[kBatch];      // lanes of the next (up to) kBatch live occurrences: wave-uniform
+                const int cnt = min(kBatch, static_cast<int>(__builtin_popcountll(m)));
+#pragma unroll
+                for (int k = 0; k < kBatch; ++k) {
+                    tt[k] = m != 0ull ? static_cast<int>(__builtin_ctzll(m)) : 0;
+                    m &= m - 1ull;      // (0 stays 0)
+                }
+                Vec<VEC> g[kBatch];
+#pragma unroll
+                for (int k = 0; k < kBatch; ++k) {
+                    if (k < cnt) {
+                        const uint64_t off =
+                            static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(bg, tt[k]))) * width + colc;
+                        g[k].load(bag_grads + off);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < kBatch; ++k) {
+                    if (k < cnt) {
+                        const float wv = __int_as_float(__builtin_amdgcn_readlane(wb, tt[k]));
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) {
+                            const float t = __fmul_rn(scale, __fmul_rn(wv, g[k].get(e)));
+                            acc.set(e, step<kModeSgd>(acc.get(e), t, -1.0f));
+                            acc2.set(e, step<kModeSgd>(acc2.get(e), t, -1.0f));
+                        }
+                    }
+                }
+            }
+        };
+        chain(live0, bg0, wb0);
+        bool dead = dead0;
+        // ---- the run goes on behind the window: blocks of kWcacheTrip * 64 positions from p + 48
+        if (fwd >= 48 && p + 48 < n) {
+            int base = p + 48;
+            uint32_t kq[kWcacheTrip];
+            int pq[kWcacheTrip];
+#pragma unroll
+            for (int k = 0; k < kWcacheTrip; ++k) {
+                const int at = min(base + k * kWave + lane, n - 1);
+                kq[k] = sorted[at];
+                pq[k] = perm[at];
+            }
+            bool more = true;
+            while (more) {
+                int bg[kWcacheTrip], wb[kWcacheTrip], cnt[kWcacheTrip];
+#pragma unroll
+                for (int k = 0; k < kWcacheTrip; ++k) {
+                    bg[k] = bag_at(pq[k]);
+                    wb[k] = __float_as_int(weights[pq[k]]);
+                    // the run is contiguous: its positions of this block are a prefix of the block
+                    const unsigned long long mk = __ballot(base + k * kWave + lane < n && kq[k] == key);
+                    cnt[k] = (~mk == 0ull) ? kWave : static_cast<int>(__builtin_ctzll(~mk));
+                }
+                more = cnt[kWcacheTrip - 1] == kWave && base + kWcacheTrip * kWave < n;
+#pragma unroll
+                for (int k = 0; k + 1 < kWcacheTrip; ++k)
+                    more = more && cnt[k] == kWave;
+                const int nbase = base + kWcacheTrip * kWave;
+                if (more) {
+#pragma unroll
+                    for (int k = 0; k < kWcacheTrip; ++k) {
+                        const int at = min(nbase + k * kWave + lane, n - 1);
+                        kq[k] = sorted[at];
+                        pq[k] = perm[at];
+                    }
+                }
+                bool open = true;      // (a block behind the run's end holds none of its positions)
+#pragma unroll
+                for (int k = 0; k < kWcacheTrip; ++k) {
+                    const bool ink = open && lane < cnt[k];
+                    const bool lv = (wb[k] & 0x7FFFFFFF) != 0;
+                    const unsigned long long m = __ballot(ink && lv);
+                    dead = dead || __ballot(ink && !lv) != 0ull;
+                    chain(m, bg[k], wb[k]);
+                    open = open && cnt[k] == kWave;
+                }
+                base = nbase;
+            }
+        }
+        if (dead) {      // (wave-uniform) every dead occurrence of the run at once
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                acc.set(e, step<kModeSgd>(acc.get(e), z, -1.0f));
+                acc2.set(e, step<kModeSgd>(acc2.get(e), z, -1.0f));
+            }
+        }
+        if (colok) {
+            if (push)
+                push_epilogue<VEC>(push, col, acc, push2, keep);
+            acc.store(dst_row + col);
+            if (d2on)
+                acc2.store(d2row + col);
+        }
+    }
 }
 
 // ---- the update of a planned batch: ONE launch -----------------------------------------------------------------------------
@@ -1298,15 +1516,21 @@ __global__ __launch_bounds__(kSumWaves *kWave) void cache_lookup_sum_planned_ker
 // BAGS (ha_cache_update_planned_bags): `grads` is the POOLED gradient [nbags, width]; the source row of occurrence i is its bag
 // -- i / maps.valdiv (fixed bags) or maps.valmap[i] (ragged: bag_of) --, read in place of row i of an expanded [n, width]
 // tensor: the same values in the same order, so the same bits.  The meta and evict roles do not read gradients.
+// WEIGHTED (ha_cache_update_planned_wbags): the accumulate role is cache_wbags_accumulate above, which needs no workgroup
+// memory and more registers than apply_body's budget leaves: launch bounds of its own.  The other instantiations ignore `wa`.
 constexpr int kPlanEvictBlocks = 64, kPlanMetaBlocks = 8;
-template <int VEC, bool BAGS = false>
-__global__ __launch_bounds__(1024, 8) void cache_update_planned_kernel(
+template <int VEC, bool BAGS = false, bool WEIGHTED = false>
+__global__ __launch_bounds__(1024, WEIGHTED ? 4 : 8) void cache_update_planned_kernel(
     Cache c, const uint32_t *__restrict__ sorted, const int32_t *__restrict__ perm, int n, const float *__restrict__ grads,
     ApplyMaps maps, const int32_t *__restrict__ it_upd_pos, const long long *__restrict__ pver,
     const int32_t *__restrict__ ev_slot, const uint32_t *__restrict__ ev_key, const int32_t *__restrict__ ev_upd,
-    const PlanRec *__restrict__ rec, int pkmode) {
+    const PlanRec *__restrict__ rec, int pkmode, WbagArgs wa) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_apply[];
     const int b = blockIdx.x;
+    if (WEIGHTED && b >= kPlanMetaBlocks + kPlanEvictBlocks) {      // (launched without workgroup memory)
+        cache_wbags_accumulate<VEC>(c, sorted, perm, n, grads, maps, wa, b - kPlanMetaBlocks - kPlanEvictBlocks);
+        return;
+    }
     if (b >= kPlanMetaBlocks + kPlanEvictBlocks) {
         apply_body<kModeSgd, VEC, 2, kHandNone, BAGS>(c.grad, static_cast<uint64_t>(c.S), static_cast<int>(c.width), sorted, perm,
                                                       nullptr, n, grads, -1.0f, b - kPlanMetaBlocks - kPlanEvictBlocks, s_apply,
@@ -2202,19 +2426,49 @@ static int update_rows(ha_cache *h, hipStream_t s, void *ws, int64_t n, const fl
         maps.valdiv = bag_of ? 0 : static_cast<int>(bag);
         if (vec_ok)
             hipLaunchKernelGGL((cache_update_planned_kernel<4, true>), grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm,
-                               (int)n, grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+                               (int)n, grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode, WbagArgs{});
         else
             hipLaunchKernelGGL((cache_update_planned_kernel<1, true>), grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm,
-                               (int)n, grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+                               (int)n, grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode, WbagArgs{});
         HA_LAUNCH_CHECK();
         return 0;
     }
     if (vec_ok)
         hipLaunchKernelGGL(cache_update_planned_kernel<4>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
-                           grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+                           grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode, WbagArgs{});
     else
         hipLaunchKernelGGL(cache_update_planned_kernel<1>, grid, dim3(1024), kApplyLdsBytes, s, c, p.sorted, p.perm, (int)n,
-                           grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode);
+                           grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode, WbagArgs{});
+    HA_LAUNCH_CHECK();
+    return 0;
+}
+// the row launch of a planned update from weighted bags (cache_update_planned_kernel<.., WEIGHTED>): update_rows' arguments,
+// the pooled gradient [nbags, width], the n weights and the scale
+static int update_rows_wbags(ha_cache *h, hipStream_t s, void *ws, int64_t n, const float *bag_grads, const float *weights,
+                             float scale, int64_t nbags, const int4 *pos_item, const int32_t *it_upd_pos, const long long *pver,
+                             const int32_t *ev_slot, const uint32_t *ev_key, const int32_t *ev_upd, const PlanRec *rec, int pkmode,
+                             int64_t bag, const int32_t *bag_of) {
+    Cache &c = h->c;
+    PlanPtrs p = plan_layout(ws, n);
+    const int apply_blocks = static_cast<int>((n + kPosPerBlock - 1) / kPosPerBlock);
+    ApplyMaps maps{};
+    maps.dst2 = c.data;
+    maps.push_tab = c.table;
+    maps.push_rows = static_cast<uint64_t>(c.store_rows);
+    maps.pos_item = pos_item;
+    maps.victim_row = reinterpret_cast<const int *>(&rec->vh_slot);
+    maps.valmap = bag_of;
+    maps.valdiv = bag_of ? 0 : static_cast<int>(bag);
+    const bool vec_ok = (c.width % 4 == 0) && (reinterpret_cast<uintptr_t>(bag_grads) % 16 == 0) &&
+                        (reinterpret_cast<uintptr_t>(c.table) % 16 == 0);
+    const dim3 grid(static_cast<unsigned>(apply_blocks + kPlanEvictBlocks + kPlanMetaBlocks));
+    const WbagArgs wa{weights, scale, static_cast<uint32_t>(nbags)};
+    if (vec_ok)
+        hipLaunchKernelGGL((cache_update_planned_kernel<4, true, true>), grid, dim3(1024), 0, s, c, p.sorted, p.perm, (int)n,
+                           bag_grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode, wa);
+    else
+        hipLaunchKernelGGL((cache_update_planned_kernel<1, true, true>), grid, dim3(1024), 0, s, c, p.sorted, p.perm, (int)n,
+                           bag_grads, maps, it_upd_pos, pver, ev_slot, ev_key, ev_upd, rec, pkmode, wa);
     HA_LAUNCH_CHECK();
     return 0;
 }
@@ -2244,8 +2498,9 @@ static uint64_t sum_blocks(const Cache &c, int64_t nbags, const float *out, int 
 }
 
 // the row launch of a planned lookup delivered sum-pooled (entry i of the slot) / of a chain step's pooled pull half (pp)
+// (weights != nullptr: the weighted form, cache_lookup_sum_planned_kernel<.., WEIGHTED>; never with pp)
 static int lookup_sum_rows(ha_cache *h, hipStream_t s, PlanSlot *sl, int i, int64_t n, int64_t nbags, int64_t bag,
-                           const int64_t *offsets, float *out, bool pp, const char *who) {
+                           const int64_t *offsets, float *out, bool pp, const char *who, const float *weights = nullptr) {
     Cache &c = h->c;
     const long long at = static_cast<long long>(i) * c.nmax;
     PlanPtrs p = plan_layout(sl->ws[i], n);
@@ -2260,12 +2515,15 @@ static int lookup_sum_rows(ha_cache *h, hipStream_t s, PlanSlot *sl, int i, int6
     const dim3 grid(static_cast<unsigned>(blocks64)), block(kSumWaves * kWave);
 #define HA_SUM_CASE(V, R)                                                                                                    \
     do {                                                                                                                     \
-        if (pp)                                                                                                              \
+        if (weights)                                                                                                         \
+            hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R, false, true>), grid, block, 0, s, c, sp, (long long)n, \
+                               (long long)bag, offsets, (long long)nbags, nslice, out, weights);                             \
+        else if (pp)                                                                                                         \
             hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R, true>), grid, block, 0, s, c, sp, (long long)n,        \
-                               (long long)bag, offsets, (long long)nbags, nslice, out);                                      \
+                               (long long)bag, offsets, (long long)nbags, nslice, out, (const float *)nullptr);              \
         else                                                                                                                 \
             hipLaunchKernelGGL((cache_lookup_sum_planned_kernel<V, R, false>), grid, block, 0, s, c, sp, (long long)n,       \
-                               (long long)bag, offsets, (long long)nbags, nslice, out);                                      \
+                               (long long)bag, offsets, (long long)nbags, nslice, out, (const float *)nullptr);              \
     } while (0)
     if (vec == 4) {
         if (few) HA_SUM_CASE(4, 8); else HA_SUM_CASE(4, 32);
@@ -2400,6 +2658,96 @@ extern "C" int ha_cache_update_planned_bags(ha_cache *h, int64_t n, const float 
         const long long at = static_cast<long long>(i) * c.nmax;
         if (update_rows(h, s, sl->ws[i], n, bag_grads, sl->pos_item + at, sl->it_upd_pos + at, sl->pver + at, sl->ev_slot + at,
                         sl->ev_key + at, sl->ev_upd + at, sl->rec + i, sl->pk[i] ? 1 : 0, bag_of ? 0 : bag, bag_of))
+            return -1;
+    }
+    cache_mark(h, kTEnd, s);
+    h->settle_slot = nullptr;
+    h->evict_empty = true;
+    return plan_called(h, sl, i, 1, s);
+}
+
+// The lookup of the next planned batch, delivered as WEIGHTED sums of its bags (cache_lookup_sum_planned_kernel<.., WEIGHTED>):
+// per bag and column acc = +0, then acc = fl(acc + fl(w_j * r_j)) over the occurrences with w_j != 0 in position order, r_j the row
+// ha_cache_lookup_planned writes.  weights: n floats on the device.  Takes ha_cache_lookup_planned's place in the slot's call
+// sequence and leaves the cache in the same state, whatever the weights are.
+extern "C" int ha_cache_lookup_wsum_planned(ha_cache *h, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets,
+                                            const float *weights, float *out, ha_stream_t stream) {
+    HA_REQUIRE(h, "cache_lookup_wsum_planned: null handle");
+    HA_REQUIRE(n >= 0 && nbags >= 0 && nbags < (1ll << 31) && bag >= 0, "cache_lookup_wsum_planned: bad sizes n=%ld nbags=%ld bag=%ld",
+               (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE((bag >= 1) != (offsets != nullptr), "cache_lookup_wsum_planned: give exactly one of bag >= 1 and offsets (bag=%ld, "
+               "offsets %s)", (long)bag, offsets ? "given" : "null");
+    HA_REQUIRE(offsets != nullptr || (n % bag == 0 && n / bag == nbags), "cache_lookup_wsum_planned: n=%ld is not nbags=%ld bags of "
+               "bag=%ld ids", (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(n == 0 || nbags >= 1, "cache_lookup_wsum_planned: %ld ids in no bag", (long)n);
+    HA_REQUIRE(nbags == 0 || out, "cache_lookup_wsum_planned: null output");
+    HA_REQUIRE(n == 0 || weights, "cache_lookup_wsum_planned: %ld ids, but no weights", (long)n);
+    int i = 0;
+    PlanSlot *sl = plan_current(h, 0, &i);
+    HA_REQUIRE(sl == nullptr || !sl->pp, "cache_lookup_wsum_planned: the planned block is a push-pull chain (ha_cache_plan_block_push_pull): "
+               "its steps are not pooled by this call -- ha_cache_push_pull_planned_bags serves the chain's entries pooled");
+    HA_REQUIRE(!h->chain_open, "cache_lookup_wsum_planned: a planned push-pull chain is open: its steps are not pooled by this call "
+               "(ha_cache_push_pull_planned_bags)");
+    HA_REQUIRE(sl != nullptr, "cache_lookup_wsum_planned: no planned batch is due for its lookup (ha_cache_plan_block; lookup and "
+               "update alternate)");
+    HA_REQUIRE(sl->n[i] == n, "cache_lookup_wsum_planned: the planned batch has %ld keys (got %ld)", (long)sl->n[i], (long)n);
+    if (nbags > 0) {
+        int vec = 1;
+        uint32_t nslice = 1;
+        HA_REQUIRE(sum_blocks(h->c, nbags, out, &vec, &nslice) < (1ull << 31), "cache_lookup_wsum_planned: batch too large");
+    }
+    hipStream_t s = as_stream(stream);
+    if (!sl->waited) {
+        HA_CHECK_HIP(hipStreamWaitEvent(s, sl->booked, 0));
+        sl->waited = true;
+    }
+    cache_mark(h, kTStart, s, true);
+    // (n == 0 with bags to fill: every bag is empty and its sum is zeros with or without weights -- the unweighted launch)
+    if (nbags > 0 && lookup_sum_rows(h, s, sl, i, n, nbags, bag, offsets, out, false, "cache_lookup_wsum_planned",
+                                     n > 0 ? weights : nullptr))
+        return -1;
+    cache_mark(h, kTEnd, s);
+    h->settle_slot = nullptr;
+    h->settle_idx = i;
+    return plan_called(h, sl, i, 0, s);
+}
+
+// The update of the planned batch from the pooled gradient [nbags, width] of WEIGHTED bags: ha_cache_update_planned on the
+// [n, width] tensor whose row i is fl(scale * fl(w_i * bag_grads[bag(i), :])) for w_i != 0 and fl(scale * +0) otherwise -- what
+// ha_wbag_grad_rows followed by a multiplication by scale produces --, bit for bit, without that tensor
+// (cache_update_planned_kernel<.., WEIGHTED>).  weights: n floats on the device; scale must be finite.  The bookkeeping, the versions
+// and which lines are pushed do not depend on the weights.
+extern "C" int ha_cache_update_planned_wbags(ha_cache *h, int64_t n, const float *bag_grads, const float *weights, float scale,
+                                             int64_t nbags, int64_t bag, const int32_t *bag_of, ha_stream_t stream) {
+    HA_REQUIRE(h, "cache_update_planned_wbags: null handle");
+    HA_REQUIRE(n >= 0 && nbags >= 0 && nbags < (1ll << 31) && bag >= 0 && bag < (1ll << 31),
+               "cache_update_planned_wbags: bad sizes n=%ld nbags=%ld bag=%ld", (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(std::isfinite(scale), "cache_update_planned_wbags: scale must be finite (got %g)", (double)scale);
+    // (an empty batch of ragged bags has no bag_of to give: neither is accepted then)
+    HA_REQUIRE(n == 0 ? !(bag >= 1 && bag_of != nullptr) : (bag >= 1) != (bag_of != nullptr),
+               "cache_update_planned_wbags: give exactly one of bag >= 1 and bag_of (bag=%ld, bag_of %s)", (long)bag,
+               bag_of ? "given" : "null");
+    HA_REQUIRE(bag < 1 || (n % bag == 0 && n / bag == nbags), "cache_update_planned_wbags: n=%ld is not nbags=%ld bags of "
+               "bag=%ld ids", (long)n, (long)nbags, (long)bag);
+    HA_REQUIRE(n == 0 || (nbags >= 1 && bag_grads && weights), "cache_update_planned_wbags: %ld ids, but no bags, no gradient or "
+               "no weights", (long)n);
+    int i = 0;
+    PlanSlot *sl = plan_current(h, 1, &i);
+    HA_REQUIRE(sl == nullptr || !sl->pp, "cache_update_planned_wbags: the planned block is a push-pull chain "
+               "(ha_cache_plan_block_push_pull): its steps are not pooled by this call -- ha_cache_push_pull_planned_bags serves the "
+               "chain's entries pooled");
+    HA_REQUIRE(!h->chain_open, "cache_update_planned_wbags: a planned push-pull chain is open: its steps are not pooled by this call "
+               "(ha_cache_push_pull_planned_bags)");
+    HA_REQUIRE(sl != nullptr, "cache_update_planned_wbags: no planned batch is due for its update (its lookup comes first)");
+    HA_REQUIRE(sl->n[i] == n, "cache_update_planned_wbags: the planned batch has %ld keys (got %ld)", (long)sl->n[i], (long)n);
+    Cache &c = h->c;
+    hipStream_t s = as_stream(stream);
+    cache_mark(h, kTStart, s, true);
+    if (n > 0) {
+        const long long at = static_cast<long long>(i) * c.nmax;
+        if (update_rows_wbags(h, s, sl->ws[i], n, bag_grads, weights, scale, nbags, sl->pos_item + at, sl->it_upd_pos + at,
+                              sl->pver + at, sl->ev_slot + at, sl->ev_key + at, sl->ev_upd + at, sl->rec + i, sl->pk[i] ? 1 : 0,
+                              bag_of ? 0 : bag, bag_of))
             return -1;
     }
     cache_mark(h, kTEnd, s);
@@ -2588,6 +2936,21 @@ extern "C" int ha_cache_run_planned_pairs_bags(ha_cache *h, int count, int64_t n
         if (ha_cache_lookup_sum_planned(h, n, nbags, bag, nullptr, outs[k], stream))
             return -1;
         if (ha_cache_update_planned_bags(h, n, bag_grads[k], nbags, bag, nullptr, stream))
+            return -1;
+    }
+    return 0;
+}
+
+// ... with fixed bags of `bag` ids and the weights weights[k] ([n]) of pair k: ha_cache_lookup_wsum_planned into outs[k], then
+// ha_cache_update_planned_wbags with bag_grads[k] and `scale`
+extern "C" int ha_cache_run_planned_pairs_wbags(ha_cache *h, int count, int64_t n, int64_t nbags, int64_t bag, float *const *outs,
+                                                const float *const *bag_grads, const float *const *weights, float scale,
+                                                ha_stream_t stream) {
+    HA_REQUIRE(h && count >= 0 && (count == 0 || (outs && bag_grads && weights)), "cache_run_planned_pairs_wbags: bad arguments");
+    for (int k = 0; k < count; ++k) {
+        if (ha_cache_lookup_wsum_planned(h, n, nbags, bag, nullptr, weights[k], outs[k], stream))
+            return -1;
+        if (ha_cache_update_planned_wbags(h, n, bag_grads[k], weights[k], scale, nbags, bag, nullptr, stream))
             return -1;
     }
     return 0;

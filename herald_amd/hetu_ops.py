@@ -28,11 +28,11 @@ Mirrors (paths relative to /root/reference):
                                                   straight from the pooled gradient of EmbeddingLookUpSum_Gradient)
 
 `Config` carries the HetuConfig fields those ops read (executor.py:162-182): comm_mode, bsp, prefetch,
-cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and five switches of this build: cache_plan_ahead (the cache's
+cstable_policy, cache_bound, cache_limit, use_sparse_pull -- and six switches of this build: cache_plan_ahead (the cache's
 planned flow), cache_fuse_bags (with it, at bsp 0 and on the LRU asp chain: a sum-pooled lookup is pulled and pushed pooled, see
 Config), cache_fuse_bag_calls (the same through the cache's call-by-call interface, off by default),
-ps_fuse_bags (the same on the plain PS flavour, every schedule) and ps_fuse_wbags (the WEIGHTED sum-pooled lookup of the FAE
-models pulled and pushed pooled on the plain PS flavour).  The data loader contract is the reference's
+ps_fuse_bags (the same on the plain PS flavour, every schedule), ps_fuse_wbags (the WEIGHTED sum-pooled lookup of the FAE
+models pulled and pushed pooled on the plain PS flavour) and cache_fuse_wbags (the same in the cache's planned pairs, opt-in).  The data loader contract is the reference's
 `get_arr` / `get_next_arr` (python/hetu/dataloader.py:63-98): `next_ids()` returns the ids of the batch
 after the current one.  Everything computed goes through libherald_amd.so.
 """
@@ -48,7 +48,7 @@ from .sharded import ShardedEmbedding
 class Config:
     def __init__(self, comm_mode=None, bsp=0, prefetch=True, cstable_policy=None, cache_bound=100, cache_limit=0,
                  use_sparse_pull=True, cache_perf_enable=False, cache_plan_ahead=False, cache_fuse_bags=True,
-                 ps_fuse_bags=True, cache_fuse_bag_calls=False, ps_fuse_wbags=True):
+                 ps_fuse_bags=True, cache_fuse_bag_calls=False, ps_fuse_wbags=True, cache_fuse_wbags=False):
         self.comm_mode, self.bsp, self.prefetch = comm_mode, bsp, prefetch
         # not a HetuConfig field: the cache's PLANNED flow (csrc/cache_block.hip) for the bsp-prefetch schedule -- the bookkeeping
         # of batch k + 1 runs on a side stream beside the model's step on batch k.  Needs ids one batch further ahead than
@@ -82,6 +82,13 @@ class Config:
         # without prefetch EmbeddingLookUpWeightedSum pulls them itself (ragged bags too).  The same rows per unique key cross
         # the fabric, the same bits.  False: per-occurrence rows, a weighted summing pass, the expanded gradient.
         self.ps_fuse_wbags = ps_fuse_wbags
+        # the weighted counterpart on the cache's planned pairs (the FAE models' cold table behind the cache, the reference's
+        # --cache lfu --bound 0 --bsp 0): OPT-IN.  With bsp == 0, prefetch, cache_plan_ahead, world size 1 and peek_ids, a
+        # communicate op that was given bag=F and next_weights= pulls weighted pooled rows [B, width]
+        # (embedding_lookup_wsum_planned) and pushes the weighted pooled slices as they are, -lr included
+        # (embedding_update_planned_wbags): the same bits as per-occurrence rows, a weighted summing pass and the expanded
+        # gradient.  In every other cache configuration next_weights is refused, with or without the switch.
+        self.cache_fuse_wbags = cache_fuse_wbags
         self.cstable_policy, self.cache_bound, self.cache_limit = cstable_policy, cache_bound, cache_limit
         self.use_sparse_pull = use_sparse_pull
         self.cache_perf_enable = cache_perf_enable        # executor.py: cache_perf_enable (run_hetu.py:508-515 dumps the dicts)
@@ -341,7 +348,9 @@ class EmbeddingLookUpWeightedSum(EmbeddingLookUp):
     kernel sums them out of that row buffer (ids 0 .. n-1): every path agrees bit for bit on equal rows.  The plain PS
     flavour has a pooled weighted form (Config.ps_fuse_wbags): with prefetch the buffer of a communicate op that was given
     bag= and next_weights= already holds the weighted pooled rows (store.pull_wsum) and is copied as it is; without prefetch
-    the rows come from store.pull_wsum directly, ragged bags included.  The cache tiers have none.  A communicate op that
+    the rows come from store.pull_wsum directly, ragged bags included.  The cache's planned pairs have one too, opt-in
+    (Config.cache_fuse_wbags: the op's buffer holds the rows of embedding_lookup_wsum_planned and is copied as it is); the other
+    cache flows have none.  A communicate op that
     pulls rows pooled WITHOUT weights (bag= alone) cannot serve this operator and is refused."""
 
     def forward_hook(self, config):
@@ -671,8 +680,10 @@ class ParameterServerCommunicateOp:
         returned.  On the plain PS flavour with Config.ps_fuse_wbags the op then pulls weighted pooled rows
         (store.pull_wsum; sparse_pull_val is [B, width], recorded in config.ps_wpooled, not ps_pooled) and pushes weighted
         pooled slices as they are, -lr included (store.push_wbags); with ps_fuse_wbags=False it moves per-occurrence rows and
-        the expanded gradient, as an op without bag= does (rows pooled without weights would be wrong for this lookup).  The
-        cache flavour has no pooled weighted form and refuses next_weights.  Without bag= it is ignored."""
+        the expanded gradient, as an op without bag= does (rows pooled without weights would be wrong for this lookup).  On the
+        cache flavour the planned pairs have a pooled weighted form under Config.cache_fuse_wbags (bsp == 0, prefetch,
+        cache_plan_ahead, world size 1, peek_ids): embedding_lookup_wsum_planned / embedding_update_planned_wbags; every other
+        cache configuration refuses next_weights.  Without bag= it is ignored."""
         self.parameter = parameter
         self.learning_rate = -learning_rate                           # :24
         self.next_ids = next_ids
@@ -687,14 +698,23 @@ class ParameterServerCommunicateOp:
         self._planned = None          # the planned flow: (ids, push plan or None) of the planned batches, oldest first
         self._chain = False           # the planned flow of the asp schedule: _planned = ids of a push-pull chain's batches
         self._bag_calls = False       # pooled rows through the call-by-call cache (Config.cache_fuse_bag_calls)
+        self._cache_wbags = False     # weighted pooled rows through the cache's planned pairs (Config.cache_fuse_wbags)
 
     def forward_hook(self, config, first_ids=None, barrier=lambda: None, first_weights=None):   # :130-242
         self.config, self.barrier = config, barrier
         p = self.parameter
         self.use_cache_table = config.cstable_policy is not None and p.is_embed
-        if self.use_cache_table and self.next_weights is not None:
-            raise ValueError("ParameterServerCommunicateOp(next_weights=): the cache tiers have no pooled weighted form; build "
-                             "the op without next_weights (weighted slices are then expanded before every push)")
+        cache_wbags = False
+        if self.use_cache_table and self.next_weights is not None and self.bag is not None:
+            cache_wbags = bool(getattr(config, "cache_fuse_wbags", False)) and config.bsp == 0 and bool(config.prefetch) and \
+                bool(getattr(config, "cache_plan_ahead", False)) and p.store.world == 1 and self.peek_ids is not None
+        if self.use_cache_table and self.next_weights is not None and not cache_wbags:
+            raise ValueError("ParameterServerCommunicateOp(next_weights=): the cache tiers have a pooled weighted form in the "
+                             "planned pairs only -- Config(cache_fuse_wbags=True) with bsp == 0, prefetch, cache_plan_ahead, "
+                             "world size 1, peek_ids and bag= --; otherwise build the op without next_weights (weighted slices "
+                             "are then expanded before every push)")
+        if cache_wbags and first_ids is not None and first_weights is None:
+            raise ValueError("ParameterServerCommunicateOp(next_weights=): first_ids come with first_weights")
         if self.use_cache_table:
             width = p.shape[1]
             store = p.store
@@ -728,7 +748,10 @@ class ParameterServerCommunicateOp:
                 self.compute = self._compute_bsp_prefetch
                 if getattr(config, "cache_plan_ahead", False) and store.world == 1 and self.peek_ids is not None:
                     self._planned = []        # pull(k + 1) follows push(k) of the same ids batch after batch: the planned pairs
-                    if self.bag is not None and getattr(config, "cache_fuse_bags", True):
+                    if cache_wbags:           # ... weighted pooled: embedding_lookup_wsum_planned / _update_planned_wbags
+                        self._bag, self._cache_wbags = self.bag, True
+                        self._first_weights = first_weights if first_ids is not None else None
+                    elif self.bag is not None and getattr(config, "cache_fuse_bags", True):
                         self._bag = self.bag
             elif config.prefetch:
                 self.compute = self._compute_asp_prefetch
@@ -772,7 +795,7 @@ class ParameterServerCommunicateOp:
                     raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
                                      % (self._bag, self._bag, tuple(first.shape)))
                 self.sparse_pull_val = torch.empty((first.shape[0], p.shape[1]), dtype=torch.float32, device=first.device)
-                if self._ps_wbags:
+                if self._ps_wbags or self._cache_wbags:
                     config.ps_wpooled[p] = self._bag
                 else:
                     config.ps_pooled[p] = self._bag
@@ -804,6 +827,15 @@ class ParameterServerCommunicateOp:
         if self._ps_wbags and getattr(grad, "weighted", False) and \
                 (grad.bag == self._bag if grad.bag is not None else grad.offsets is not None):
             return grad
+        if self._cache_wbags:
+            # the pull buffer holds weighted pooled rows of bags of self._bag ids: the gradients are the weighted slices of
+            # that bag size and nothing else (as _pooled_by_bag for its flow); they stay pooled, -lr goes into the push
+            if not (getattr(grad, "weighted", False) and grad.bag == self._bag):
+                raise RuntimeError("ParameterServerCommunicateOp (cache_fuse_wbags, bag=%d): the pull buffer holds weighted "
+                                   "pooled rows, so the gradients must be the weighted slices of "
+                                   "EmbeddingLookUpWeightedSum_Gradient over bags of %d ids; use cache_fuse_wbags=False and no "
+                                   "next_weights for other gradients" % (self._bag, self._bag))
+            return grad
         grad = unweighted_slices(grad)
         if not getattr(grad, "pooled", False):
             return grad
@@ -815,7 +847,7 @@ class ParameterServerCommunicateOp:
                                  push_indices=grad.push_indices)
 
     def _mult_lr(self, grad):
-        if self._ps_wbags and getattr(grad, "weighted", False):
+        if (self._ps_wbags or self._cache_wbags) and getattr(grad, "weighted", False):
             # (what _per_occurrence left weighted: -lr goes to push_wbags, which rounds fl(-lr * fl(w * g)) as wbag_grad_rows,
             # scale_ and a push with scale 1 do; the caller's values and weights are not written)
             return
@@ -882,6 +914,9 @@ class ParameterServerCommunicateOp:
                 raise RuntimeError("ParameterServerCommunicateOp (cache_plan_ahead): the gradients pushed are not those of the "
                                    "batch pulled last, or not with the push plan it was planned with")
             self._planned.pop(0)
+            if self._cache_wbags:      # (what _per_occurrence left weighted: vals is [B, width]; learning_rate is -lr)
+                return self.cache.embedding_update_planned_wbags(vals.contiguous(), grad.weights.reshape(-1).contiguous(),
+                                                                 bag=self._bag, scale=self.learning_rate)
             if self._bag is not None and getattr(grad, "pooled", False):      # vals is [B, width]: one row per bag
                 return self.cache.embedding_update_planned_bags(vals.contiguous(), bag=self._bag)
             return self.cache.embedding_update_planned(vals)     # (a planned plan: cache.cc:248-335, _embeddingUpdateWithPushKeys)
@@ -934,6 +969,15 @@ class ParameterServerCommunicateOp:
             nxt = self.peek_ids(self._peek_offset)                 # the batch after this one: its bookkeeping runs from now on,
             if nxt is not None:                                    # beside this batch's rows and the model's step
                 self._plan(nxt)
+            if self._cache_wbags:
+                shaped = ids[0] if isinstance(ids, tuple) else ids
+                if shaped.dim() != 2 or shaped.shape[1] != self._bag:
+                    raise ValueError("ParameterServerCommunicateOp(bag=%d): ids must be [B, %d], got %s"
+                                     % (self._bag, self._bag, tuple(shaped.shape)))
+                weights, self._first_weights = self._first_weights, None
+                if weights is None:
+                    weights = self.next_weights()      # of the batch the latest next_ids() call returned: these ids
+                return self.cache.embedding_lookup_wsum_planned(dest, weights.reshape(-1).contiguous(), bag=self._bag)
             if self._bag is not None:
                 return self.cache.embedding_lookup_sum_planned(dest, bag=self._bag)
             return self.cache.embedding_lookup_planned(dest)      # (no next batch: the next pull plans for itself)

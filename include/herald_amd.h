@@ -1077,6 +1077,39 @@ int ha_cache_update_planned_bags(ha_cache *cache, int64_t n, const float *bag_gr
  * ha_cache_update_planned_bags(n, bag_grads[k], nbags, bag, NULL) */
 int ha_cache_run_planned_pairs_bags(ha_cache *cache, int count, int64_t n, int64_t nbags, int64_t bag, float *const *outs,
                                     const float *const *bag_grads, ha_stream_t stream);
+/* WEIGHTED bags in the planned pairs: the reference's FAE models over a cached cold table (embedding_lookup_op, mul_op by a 0/1
+ * mask, reduce_sum_op(axes=1); examples/ctr/tests/hybrid_fae_wdl_criteo.sh runs them with --cache lfu --bound 0 --bsp 0).
+ * weights: n device floats, one per occurrence (the batch's [nbags, bag] or [n]).  An occurrence is LIVE when its weight is not
+ * zero: +0.0f and -0.0f are zero, a NaN weight is live.  The bookkeeping is a function of the ids alone: plans, hits, misses,
+ * slots, victims, versions, update counters, pushes and evictions never look at a weight; the padding id is a key like any other.
+ *
+ * ha_cache_lookup_wsum_planned: per bag and column acc = +0.0f, then over the LIVE occurrences j of the bag in position order
+ * acc = fl(acc + fl(w_j * r_j)) -- one __fmul_rn and one __fadd_rn, no FMA --, r_j the row ha_cache_lookup_planned would have
+ * written for occurrence j (a pulled line with a gradient buffer: store row + gradient; a key without a line: zeros).  Bit for
+ * bit ha_cache_lookup_planned followed by ha_gather_wsum over the ids 0 .. n-1; all-ones weights give
+ * ha_cache_lookup_sum_planned.  The cache is left exactly as the unpooled lookup leaves it: a DEAD head occurrence of a pulled
+ * key still refreshes its line with the unweighted row and stages its version.  Bags, offsets, the place in the call sequence
+ * and the perf record: ha_cache_lookup_sum_planned's.
+ *
+ * ha_cache_update_planned_wbags: ha_cache_update_planned on the [n, width] tensor whose row i is
+ * t_i = fl(scale * fl(w_i * bag_grads[bag(i), :])) when w_i is not zero and fl(scale * +0.0f) otherwise (+0 for scale >= 0, -0
+ * for scale < 0, whatever bag_grads holds there) -- what ha_wbag_grad_rows followed by a multiplication by scale produces --,
+ * bit for bit, in bound mode and in push-key mode: gradient buffers, data rows, the store rows of pushed and evicted lines,
+ * versions and hasgrad are that call's.  scale must be finite.  No gradient row of a dead occurrence is read.  bag / bag_of:
+ * as ha_cache_update_planned_bags; a bag_of entry beyond nbags - 1 reads row nbags - 1 (ha_wbag_grad_rows' clamp).
+ * With all-ones weights and scale 1 the call is ha_cache_update_planned_bags.
+ *
+ * Weighted, sum-pooled and unpooled calls may be mixed freely within a block.  Both calls refuse a push-pull chain block and an
+ * open chain, as the _bags calls do. */
+int ha_cache_lookup_wsum_planned(ha_cache *cache, int64_t n, int64_t nbags, int64_t bag, const int64_t *offsets,
+                                 const float *weights, float *out, ha_stream_t stream);
+int ha_cache_update_planned_wbags(ha_cache *cache, int64_t n, const float *bag_grads, const float *weights, float scale,
+                                  int64_t nbags, int64_t bag, const int32_t *bag_of, ha_stream_t stream);
+/* `count` planned pairs of n ids in fixed bags by one call: ha_cache_lookup_wsum_planned(n, nbags, bag, NULL, weights[k], outs[k])
+ * then ha_cache_update_planned_wbags(n, bag_grads[k], weights[k], scale, nbags, bag, NULL) */
+int ha_cache_run_planned_pairs_wbags(ha_cache *cache, int count, int64_t n, int64_t nbags, int64_t bag, float *const *outs,
+                                     const float *const *bag_grads, const float *const *weights, float scale,
+                                     ha_stream_t stream);
 /* The planned flow of a PUSH-PULL CHAIN: CacheBase::_embeddingPushPull (cache.cc:356-422), the one cache call per step of the
  * asp-with-prefetch schedule (python/hetu/gpu_ops/ParameterServerCommunicate.py:37-40, 68-72): step = push_pull(pull = the ids of
  * batch k + 1, push = the ids and gradients of batch k).  LRU over a local store only (the LFU policies' planned bookkeeping
