@@ -189,6 +189,13 @@ int cpu_SGDOptimizerSparseUpdate(DLArrayHandle param,
  * workgroups of their own sum, the chunk sums added in chunk order (tree_coop_chunked; the rule: listed_chunking) -- for
  * batches in which one key's run is the launch's critical path; at BASELINE configs[2]'s shape it is not (34.5 us without,
  * 35.8 with), so 1 is what bench.py's N>1 leg uses.  ha_get_tolerance_mode returns 0 / 1 / 2.
+ * The trees read and write 16 bytes at a time: they serve rows of a multiple of 4 floats whose table and gradient pointers are
+ * 16-byte aligned.  Any other call (width % 4 != 0, a misaligned view) is the serial chain in every mode, bit for bit
+ * (oracle/qstep_model.py tolerance_has_tree).
+ * Values: a tree slot beyond the run's end holds +0 whatever lies there in memory (a select, never value * 0), and every
+ * partial sum starts from +0, so 0 + (-0) = +0 as in the reduce of ha_dedup_reduce; a NaN or an infinity stays in the key and
+ * column it sits in.  `row - tree_sum` and the chain may differ in the SIGN OF A ZERO: g and -g over a -0 row end in +0 along
+ * the chain and in -0 - (+0) = -0 through a tree (oracle/qstep_model.py states both).
  * Read at launch time by ha_sgd_apply*, ha_push_apply*, ha_dedup_reduce*, ha_apply_mapped, ha_shard_serve_push and the
  * entry points built on them (not by ha_sgd_push_pull_* / ha_step_*, which are bit-exact throughout, nor by
  * ha_qstep_* / ha_qapply, which have their own documented tolerance classes). */

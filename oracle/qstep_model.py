@@ -114,7 +114,15 @@ def listed_chunking(ids, width):
     return total > listed.size and total * nslice * 64 <= 2 * n
 
 
-def sgd_sparse_update(table, ids, grads, lr, long_min=LONG_MIN, coop_min=COOP_MIN, mode="sgd", chunked=False):
+def tolerance_has_tree(width, aligned=True):
+    """Whether the tolerance mode of the plan-driven applies (ha_set_tolerance_mode) sums long runs by its tree: the tree reads
+    and writes 16 bytes at a time (csrc/scatter_dev.h coop_slices), so it serves rows of a multiple of 4 floats whose table
+    and gradients start on 16 bytes (`aligned`); every other call keeps the serial chain in every mode (include/herald_amd.h,
+    ha_set_tolerance_mode).  sgd_sparse_update applies the rule itself when it restates the mode (long_min=None)."""
+    return width % 4 == 0 and bool(aligned)
+
+
+def sgd_sparse_update(table, ids, grads, lr, long_min=LONG_MIN, coop_min=COOP_MIN, mode="sgd", chunked=False, aligned=True):
     """In place: table after one ha_qstep apply of (ids, grads).  ids: integer array (keys beyond the table are
     ignored, as by the library).
 
@@ -123,7 +131,10 @@ def sgd_sparse_update(table, ids, grads, lr, long_min=LONG_MIN, coop_min=COOP_MI
     where ha_qstep cuts runs beyond 256 occurrences into chunks; chunked=True: so do the applies of a finished plan when
     listed_chunking(ids, width) holds --; everything shorter is the serial chain).  mode: "sgd" row - sum(lr*g) / chain row -= lr*g;  "push" row + sum(g) (lr is ignored: the
     library reduces from 0 in order, then adds once -- ha_push_apply);  the reduced rows of ha_dedup_reduce_scaled
-    are mode="push" on a zero table with grads pre-scaled."""
+    are mode="push" on a zero table with grads pre-scaled.  aligned: whether table and gradients start on 16 bytes; the
+    tolerance mode has no tree otherwise, nor on rows that are no multiple of 4 floats (tolerance_has_tree)."""
+    if long_min is None and not tolerance_has_tree(np.asarray(table).shape[1], aligned):
+        coop_min = 1 << 30
     ids = np.asarray(ids).reshape(-1).astype(np.int64)
     grads = np.asarray(grads, dtype=F).reshape(ids.size, -1)
     order = np.argsort(ids, kind="stable")
