@@ -485,6 +485,15 @@ def _refuse_fm_pooled(name, grad):
 
 
 def sgd_update_sparse(param, grad, lr, stream=None):
+    """OptimizerOp's sparse SGD branch on a device table (_sgd_update_sparse), with `stream` as torch's current stream while it
+    runs: the .contiguous() copies, the masked keys and the temporary plans of the ragged branches are enqueued on, and
+    allocated in the order of, the stream of the launches (the stream contract, ops.py)."""
+    dev = param.table.device if param.table is not None else None
+    with ops.on_stream(stream, dev):
+        _sgd_update_sparse(param, grad, lr, stream)
+
+
+def _sgd_update_sparse(param, grad, lr, stream):
     """OptimizerOp's sparse SGD branch on a device table (OptimizerLink.py:23-33): no dedup, duplicates in
     occurrence order.  Pooled slices (EmbeddingLookUpSum_Gradient) go to the bag apply: no expanded gradient is built.
     FM-pooled slices (EmbeddingLookUpFMSum_Gradient) go to the fused FM apply: the one-call form for fixed bags, sort + finish +
@@ -501,7 +510,8 @@ def sgd_update_sparse(param, grad, lr, stream=None):
                                           lr, stream=stream)
         else:
             ids = grad.indices.reshape(-1).contiguous()
-            plan = ops.IndexPlan(max(ids.numel(), 1), device=ids.device).sort(ids, stream).finish(stream)
+            plan = ops.IndexPlan.temporary(max(ids.numel(), 1), ids.device, ops._torch_stream(stream, ids.device))
+            plan.sort(ids, stream).finish(stream)
             ops.sgd_apply_fm_bags(param.table, plan, g_sum, g_fm, fm_sum, lr, bag_of=grad.bag_of, stream=stream)
         return
     if getattr(grad, "weighted_fm", False):
@@ -518,7 +528,8 @@ def sgd_update_sparse(param, grad, lr, stream=None):
                                            stream=stream)
         else:
             keys = _masked_keys(grad.indices.reshape(-1).contiguous(), weights, table.shape[0])
-            plan = ops.IndexPlan(max(keys.numel(), 1), device=keys.device).sort(keys, stream, key_limit=table.shape[0])
+            plan = ops.IndexPlan.temporary(max(keys.numel(), 1), keys.device, ops._torch_stream(stream, keys.device))
+            plan.sort(keys, stream, key_limit=table.shape[0])
             ops.sgd_apply_wfm_bags(table, plan.finish(stream), g_sum, g_sq, weights, lr, bag_of=grad.bag_of, stream=stream)
         return
     if getattr(grad, "weighted", False):
@@ -535,7 +546,8 @@ def sgd_update_sparse(param, grad, lr, stream=None):
                                         stream=stream)
         else:
             keys = _masked_keys(grad.indices.reshape(-1).contiguous(), weights, table.shape[0])
-            plan = ops.IndexPlan(max(keys.numel(), 1), device=keys.device).sort(keys, stream, key_limit=table.shape[0])
+            plan = ops.IndexPlan.temporary(max(keys.numel(), 1), keys.device, ops._torch_stream(stream, keys.device))
+            plan.sort(keys, stream, key_limit=table.shape[0])
             ops.sgd_apply_wbags(table, plan.finish(stream), values, weights, lr, bag_of=grad.bag_of, stream=stream)
         return
     if getattr(grad, "pooled", False):
@@ -546,7 +558,8 @@ def sgd_update_sparse(param, grad, lr, stream=None):
                                        stream=stream)
         else:
             ids = grad.indices.reshape(-1).contiguous()
-            plan = ops.IndexPlan(max(ids.numel(), 1), device=ids.device).sort(ids, stream)
+            plan = ops.IndexPlan.temporary(max(ids.numel(), 1), ids.device, ops._torch_stream(stream, ids.device))
+            plan.sort(ids, stream)
             ops.sgd_apply_bags(param.table, plan, values, lr, bag_of=grad.bag_of, stream=stream)
         return
     ops.dl_call("SGDOptimizerSparseUpdate",
@@ -611,6 +624,11 @@ def momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream
     """momentum_update's sparse branch (OptimizerLink.py:37-49): MomentumOptimizerSparseUpdate WITHOUT deduplication.
     Pooled slices go to ops.momentum_sparse_update_bags -- no expanded gradient is built; fuse_bags=False runs the reference's
     sequence (expanded_values, then the symbol): the same bits.  Weighted pooled slices are expanded first (unweighted_slices)."""
+    with ops.on_stream(stream, param.table.device if param.table is not None else None):
+        _momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream, fuse_bags)
+
+
+def _momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream, fuse_bags):
     grad = unweighted_slices(grad, stream)
     table, width = _sparse_args("momentum_update_sparse", param, grad, [("velocity", velocity)])
     if fuse_bags and getattr(grad, "pooled", False):
@@ -623,6 +641,11 @@ def momentum_update_sparse(param, grad, velocity, lr, momentum, nesterov, stream
 
 
 def _fused_update_sparse(name, kind, symbol, param, grad, state1, state2, hyper, scalars, stream, fuse_bags):
+    with ops.on_stream(stream, param.table.device if param.table is not None else None):      # (as sgd_update_sparse)
+        _fused_update_sparse_on(name, kind, symbol, param, grad, state1, state2, hyper, scalars, stream, fuse_bags)
+
+
+def _fused_update_sparse_on(name, kind, symbol, param, grad, state1, state2, hyper, scalars, stream, fuse_bags):
     states = [("the first state", state1)] + ([("the second state", state2)] if kind != "adagrad" else [])
     grad = unweighted_slices(grad, stream)      # weighted pooled slices: expanded first, whatever fuse_bags says
     table, width = _sparse_args(name, param, grad, states)

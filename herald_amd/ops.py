@@ -11,7 +11,17 @@ Mirrors (reference paths relative to /root/reference):
 
 torch is plumbing only: it owns the device allocations and the stream; every computation below is a
 call into libherald_amd.so.  There is no fallback: a missing library raises HeraldAmdError.
+
+The stream contract (include/herald_amd.h, next to ha_stream_t; tests/stream_contract.py holds one row per call).  For a
+call with stream=S, or with stream=None while S is torch's current stream:
+  1. everything the call enqueues runs on S, and its device inputs need only be complete on S;
+  2. unless the call returns a count to the host (IndexPlan.n_unique / export_f32, IndexedSlices.deduplicate), it never waits
+     on the host for S;
+  3. device memory the call allocates for its own use does not become reusable before S has run the launches that use it
+     (it is allocated while S is torch's current stream, so the caching allocator hands it on in S's order only);
+  4. the result is a function of the arguments alone: not of what ran before on S, nor of which stream S is.
 """
+import contextlib
 import ctypes
 import os
 
@@ -39,6 +49,24 @@ def _raw_stream(stream=None):
     """Raw hipStream_t value of `stream` (None = torch's current stream)."""
     p = _stream_ptr(stream).value
     return p if p is not None else 0
+
+
+def _torch_stream(stream, device):
+    """`stream` as a torch stream (None: torch's current stream of `device`)."""
+    if stream is None:
+        return torch.cuda.current_stream(device)
+    if isinstance(stream, int):
+        return torch.cuda.ExternalStream(stream, device=device)
+    return stream
+
+
+def on_stream(stream, device=None):
+    """Context in which `stream` (a torch stream, a raw hipStream_t value, or None = leave things as they are) is torch's
+    current stream: what a call does through torch -- a temporary, a .contiguous() copy, an intermediate -- is then enqueued
+    on the stream of its launches and allocated in that stream's order (the stream contract above)."""
+    if stream is None:
+        return contextlib.nullcontext()
+    return torch.cuda.stream(_torch_stream(stream, device))
 
 
 def _require(t, dtype, name):
@@ -136,6 +164,24 @@ class IndexPlan:
         self._view = None
         self._route_cache = None
         self._produced_on = None     # raw stream of the launch that last wrote the plan
+
+    @classmethod
+    def temporary(cls, capacity, device, stream):
+        """A plan that is a TEMPORARY of one call whose launches all run on `stream` (a torch stream): allocated and its
+        header zeroed in that stream's order, and the host does not wait (the stream contract, module docstring).  The
+        constructor serves plans that may be handed to launches on any stream, so it waits for the zero fill."""
+        self = cls.__new__(cls)
+        self.capacity = int(capacity)
+        self.device = torch.device(device if device is not None else "cuda")
+        self.nbytes = _lib.load().ha_plan_bytes(self.capacity)
+        with torch.cuda.stream(stream):
+            self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=self.device)
+            self.ws[:256].zero_()
+        self.n = 0
+        self._view = None
+        self._route_cache = None
+        self._produced_on = None
+        return self
 
     def produced_on(self, stream=None):
         """Record the stream of the launch that (re)wrote this plan; the host-side readers below wait for it."""
@@ -1035,8 +1081,8 @@ def sparse_opt_fused(kind, param, ids, grads, state1, state2=None, lr=0.01, eps=
     _require(ids, ids.dtype, "ids")
     _require(grads, torch.float32, "grads")
     n = ids.numel()
-    if plan is None:
-        plan = IndexPlan(max(n, 1), param.device)
+    if plan is None:        # a temporary of this call: in the order of the stream of its launches, no host wait
+        plan = IndexPlan.temporary(max(n, 1), param.device, _torch_stream(stream, param.device))
     hyper = (ctypes.c_float * 7)(lr, eps, beta1, beta2, beta1t, beta2t, weight_decay)
     check(fn(_OPT_KINDS[kind], _ptr(param), param.shape[0], param.shape[1], _ptr(ids), n, _ptr(grads), _ptr(state1),
              _ptr(state2) if state2 is not None else None, hyper, _ptr(plan.ws), _stream_ptr(stream)),
@@ -1056,8 +1102,8 @@ def sparse_opt_fused_bags(kind, param, ids, bag_grads, state1, state2=None, offs
     if bag_grads.numel() != nbags * param.shape[1]:
         raise ValueError("bag_grads must be [B, width]")
     fn = getattr(L, "ha_sparse_opt_fused_bags_" + _ids_fn(ids, "f32ids", "u64ids"))
-    if plan is None:
-        plan = IndexPlan(max(n, 1), param.device)
+    if plan is None:        # a temporary of this call, as in sparse_opt_fused
+        plan = IndexPlan.temporary(max(n, 1), param.device, _torch_stream(stream, param.device))
     elif plan.capacity < n:
         raise ValueError("plan capacity %d < %d ids" % (plan.capacity, n))
     hyper = (ctypes.c_float * 7)(lr, eps, beta1, beta2, beta1t, beta2t, weight_decay)
@@ -2147,21 +2193,22 @@ class IndexedSlices:
         """Per-occurrence values [n, width] of pooled slices (every occurrence a copy of its bag's row; of weighted slices
         its weight times that row, ops.wbag_grad_rows)."""
         self._no_fm_pooled("have no expanded values")
-        width = self.values.shape[-1]
-        vals = self.values.reshape(-1, width).contiguous()
-        if not self.pooled:
-            return vals
-        n = self.indices.numel()
-        if self.weighted:
-            w = self.weights.reshape(-1).contiguous()
+        with on_stream(stream, self.values.device):      # the copies and the row numbers below: on the stream of the launches
+            width = self.values.shape[-1]
+            vals = self.values.reshape(-1, width).contiguous()
+            if not self.pooled:
+                return vals
+            n = self.indices.numel()
+            if self.weighted:
+                w = self.weights.reshape(-1).contiguous()
+                if self.bag is not None:
+                    return wbag_grad_rows(vals, w, bag=int(self.bag), stream=stream)
+                return wbag_grad_rows(vals, w, bag_of=self.bag_of.reshape(-1).contiguous(), stream=stream)
             if self.bag is not None:
-                return wbag_grad_rows(vals, w, bag=int(self.bag), stream=stream)
-            return wbag_grad_rows(vals, w, bag_of=self.bag_of.reshape(-1).contiguous(), stream=stream)
-        if self.bag is not None:
-            rows = torch.arange(n, dtype=torch.int64, device=vals.device) // int(self.bag)
-        else:
-            rows = self.bag_of.reshape(-1).to(torch.int64)
-        return embedding_lookup(vals, rows, stream=stream)      # (the gather kernel: occurrence i <- row of its bag)
+                rows = torch.arange(n, dtype=torch.int64, device=vals.device) // int(self.bag)
+            else:
+                rows = self.bag_of.reshape(-1).to(torch.int64)
+            return embedding_lookup(vals, rows, stream=stream)      # (the gather kernel: occurrence i <- row of its bag)
 
     def get_dense_shape(self):
         assert self.dense_shape is not None
@@ -2189,6 +2236,11 @@ class IndexedSlices:
         self.deduplicated = False
 
     def deduplicate(self, stream=None):
+        """Synchronous: the number of unique indices shapes the result, so the host waits for `stream` (export_f32)."""
+        with on_stream(stream, self.indices.device):     # the two temporary plans and the outputs: in the stream's order
+            return self._deduplicate(stream)
+
+    def _deduplicate(self, stream):
         self._no_fm_pooled("cannot be deduplicated")
         if self.weighted:      # expanded first: ordinary unpooled slices from here on
             self.values = self.expanded_values(stream)
@@ -2198,15 +2250,16 @@ class IndexedSlices:
         ids = self.indices.reshape(-1)
         n = ids.numel()
         width = self.values.shape[-1]
-        plan = IndexPlan(max(n, 1), device=ids.device).build(ids, stream)
-        reduced = dedup_reduce(plan, self.values.reshape(n, width), stream=stream)
+        mine = _torch_stream(stream, ids.device)
+        plan = IndexPlan.temporary(max(n, 1), ids.device, mine).build(ids, stream)
+        reduced = dedup_reduce(plan, self.values.reshape(n, width).contiguous(), stream=stream)
         uniq_f32, _ = plan.export_f32(stream)
         u = uniq_f32.numel()
         self.indices = uniq_f32
         self.values = reduced[:u]
         if self.push_indices is not None:
             pids = self.push_indices.reshape(-1)
-            pplan = IndexPlan(max(pids.numel(), 1), device=pids.device).build(pids, stream)
+            pplan = IndexPlan.temporary(max(pids.numel(), 1), pids.device, mine).build(pids, stream)
             self.push_indices, _ = pplan.export_f32(stream)
         self.deduplicated = True
         return self
@@ -2215,7 +2268,8 @@ class IndexedSlices:
         self._no_fm_pooled("have no dense form")
         if self.pooled:
             raise ValueError("pooled IndexedSlices (bag / bag_of) have no dense form: values holds one row per bag")
-        dense = torch.zeros(tuple(self.get_dense_shape()), dtype=torch.float32, device=self.values.device)
-        dl_call("IndexedSlices2Dense", [self.values.contiguous(), self.indices.contiguous(), dense],
-                stream=stream)
+        with on_stream(stream, self.values.device):      # the zero fill must precede the scatter: the same stream
+            dense = torch.zeros(tuple(self.get_dense_shape()), dtype=torch.float32, device=self.values.device)
+            dl_call("IndexedSlices2Dense", [self.values.contiguous(), self.indices.contiguous(), dense],
+                    stream=stream)
         return dense

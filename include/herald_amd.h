@@ -53,6 +53,18 @@ typedef struct {
 typedef DLArray *DLArrayHandle;
 typedef DLStream *DLStreamHandle;
 
+/* The stream contract of every entry point that takes a stream (ha_stream_t, or a DLStreamHandle that points at one), and of
+ * the Python functions built on them (herald_amd/ops.py, herald_amd/hetu_ops.py: `stream=S`, or `stream=None` while S is
+ * torch's current stream).  tests/stream_contract.py holds one row per call; tests/test_gpu_stream_contract.py checks it.
+ *   1. Everything the call enqueues runs on S.  Its device inputs need only be complete on S.
+ *   2. Unless the call returns a count to the host (the n_unique of a plan: IndexPlan.n_unique / export_f32,
+ *      IndexedSlices.deduplicate and the fuse_bags=False forms that run it), it never waits on the host for S.  (The first
+ *      call of a size on a stream may: the per-stream scratch grows.)
+ *   3. Device memory the call allocates for its own use does not become reusable before S has run the launches that use it.
+ *      In this library that is the per-stream scratch (one request per call, never from a nested call); in the Python layer,
+ *      temporaries allocated while S is torch's current stream.
+ *   4. The result is a function of the arguments alone: it does not depend on what ran before on S -- the scratch a call finds
+ *      holds whatever the last call on S left there -- nor on which stream S is. */
 typedef void *ha_stream_t; /* hipStream_t */
 
 /* ---- library / error handling ------------------------------------------- */
